@@ -93,11 +93,44 @@ def parse():
     ap.add_argument("--sync-bn", action="store_true",
                     help="N > 1: BatchNorm statistics over all ranks (the reference's SyncBatchNorm conversion): one small "
                          "collective per BatchNorm layer and pass, issued between two parts of the executor's op list")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (loss and the network's outputs, "
+                         "rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all: the same arguments give "
+                         "the same inputs, so two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 MFMA_FP32_PEAK_TFLOPS = 157.3      # dense fp32 matrix peak (v_mfma_f32_32x32x2_f32: 256 FLOP/clk/CU x 256 CUs x 2.4 GHz)
 C1_ROOM, C1_POINTS = (3.0, 3.0, 2.4), 10000      # BASELINE configs[0] / SURVEY 8d C1: single 10 k-pt room (seed 0)
+DUMP_BYTES = 64 * 10 ** 6          # --dump-outputs: array bytes in all (the .npy headers fit in the rest of 64 MiB)
+
+
+def dump_outputs(path, loss, ret):
+    """--dump-outputs: what one step returned to its caller (harness.train_step -> loss, ret) as ``path/<name>.npy``,
+    float64 where the step computed float64, else float32.  At most DUMP_BYTES in all: arrays are written smallest
+    first, each within an even share of what is left; one over its share keeps a sample of its rows drawn by a fixed
+    seed (sorted, so the same shapes give the same rows in every run)."""
+    arrays = {"loss": loss}
+    arrays.update({k: v for k, v in ret.items() if torch.is_tensor(v)})
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    left, todo = DUMP_BYTES, len(host)
+    for name in sorted(host, key=lambda n: (host[n].nbytes, n)):
+        a = host[name]
+        share = left // todo
+        if a.nbytes > share:
+            keep = share // (a.nbytes // a.shape[0])
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+            sys.stderr.write(f"bench.py: --dump-outputs {name}: {keep} of {host[name].shape[0]} rows (seeded sample)\n")
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        todo -= 1
 
 
 def self_launch(args):
@@ -693,7 +726,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step()
+        loss, ret = step()
     fence()
     elapsed = time.perf_counter() - t0
     if use_dist:
@@ -702,6 +735,8 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     scenes_per_s = world * spg * args.steps / elapsed
+    if args.dump_outputs and rank == 0:     # before the instrumented steps below overwrite them
+        dump_outputs(args.dump_outputs, loss, ret)
 
     # ---- roofline of the dominant kernel: event-instrumented extra steps (same inputs, same process) ----
     roof = None
