@@ -16,7 +16,10 @@ import harness
 import pointgroup_ops
 import spconv
 import torch_scatter
+import wsis_native as _n
 from spconv import ops
+
+import conv_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -186,59 +189,78 @@ def test_c4_one_million_points_inference_slice():
 
 
 # ---------------------------------------------------------------- full-size VALUE checks against the oracle's tables
+# launch-plan hints of the weight gradient (wsis_hint_batch_rows): none (one 4-wave workgroup per CU) and four scenes
+# (two): different slab counts, so a different summation order and a different walk of every wave
+HINTS = (0, 625000)
+
+
 def _oracle_rows_check(indices_host, shape, cin, cout, n_rows, seed, kind="subm"):
-    """sparse conv forward / dIn / two offsets of dW of a full-size level against an fp64 gather-GEMM whose pair lists
-    come from the ORACLE (oracle/spconv_ref.subm_pairs_fast / down_pairs_fast: numpy, independent of csrc/rulebook.hip),
-    on ``n_rows`` random output rows; tolerance 1e-5 of the tensor scale (fp32 fma chains of <= 27 * cin terms)."""
+    """sparse conv forward / dIn on ``n_rows`` random rows and ALL K offsets of dW of a full-size level against fp64
+    gather-GEMMs whose pair lists come from the ORACLE (oracle/spconv_ref.subm_pairs_fast / down_pairs_fast /
+    inverse_pairs: numpy, independent of csrc/rulebook.hip; tests/conv_ref.py).  kind: "subm" (3x3x3), "down" (k2 s2 from
+    the level of ``indices_host``) or "inverse" (the SparseInverseConv3d back to that level: input = the coarse rows of
+    its strided conv, tables nbr_up_p / order_up).  dW under both launch plans (HINTS).  Tolerance 1e-5 of the tensor's
+    max-abs (fp32 fma chains of <= 27 * cin terms per output, per-wave slice sums + fixed-order slab sums for dW); for dW
+    the reference with one pair removed must fail the same bound."""
     from oracle import spconv_ref as ref
+    lib = _n.hip()
     g = torch.Generator().manual_seed(seed)
     idx_d = torch.from_numpy(indices_host).to(DEV)
     M = indices_host.shape[0]
+    batch = int(indices_host[:, 0].max()) + 1
+    out_idx = None
     if kind == "subm":
         pairs = ref.subm_pairs_fast(indices_host, shape, 3, 1)
         mod = spconv.SubMConv3d(cin, cout, 3, padding=1, bias=False, indice_key="v").to(DEV)
-        M_out = M
-    else:
-        out_idx, out_shape, pairs = ref.down_pairs_fast(indices_host, shape, 2, 2, 0)
+        M_in = M_out = M
+        make_input = lambda x: spconv.SparseConvTensor(x, idx_d, np.array(shape), batch)
+    elif kind == "down":
+        out_idx, _, pairs = ref.down_pairs_fast(indices_host, shape, 2, 2, 0)
         mod = spconv.SparseConv3d(cin, cout, 2, stride=2, bias=False, indice_key="v").to(DEV)
-        M_out = out_idx.shape[0]
+        M_in, M_out = M, out_idx.shape[0]
+        make_input = lambda x: spconv.SparseConvTensor(x, idx_d, np.array(shape), batch)
+    else:
+        coarse, coarse_shape, down = ref.down_pairs_fast(indices_host, shape, 2, 2, 0)
+        pairs = ref.inverse_pairs(down)
+        rb = ops.build_down_rulebook(idx_d, shape, [2] * 3, [2] * 3, [0] * 3)
+        assert np.array_equal(rb.out_indices.cpu().numpy(), np.asarray(coarse, dtype=np.int32))
+        mod = spconv.SparseInverseConv3d(cin, cout, 2, indice_key="v", bias=False).to(DEV)
+        M_in, M_out = coarse.shape[0], M
+
+        def make_input(x):
+            t = spconv.SparseConvTensor(x, rb.out_indices, np.array(coarse_shape), batch)
+            t.indice_dict["v"] = rb
+            return t
     K = len(pairs)
-    x = torch.randn(M, cin, generator=g).to(DEV).requires_grad_(True)
-    t = spconv.SparseConvTensor(x, idx_d, np.array(shape), int(indices_host[:, 0].max()) + 1)
-    out = mod(t)
-    y = out.features
-    assert y.shape == (M_out, cout)
-    if kind != "subm":      # strided conv: output rows in ascending linear index = the oracle's order
-        assert np.array_equal(out.indices.cpu().numpy(), np.asarray(out_idx, dtype=np.int32))
+    pairs_d = conv_ref.device_pairs(pairs, DEV)
+    x = torch.randn(M_in, cin, generator=g).to(DEV)
     gy = torch.randn(M_out, cout, generator=g).to(DEV)
-    y.backward(gy)
-    W = mod.weight.detach().view(K, cin, cout).double()
-    xd, gyd = x.detach().double(), gy.double()
-    rows_o = torch.randint(0, M_out, (n_rows,), generator=g).to(DEV)
-    rows_i = torch.randint(0, M, (n_rows,), generator=g).to(DEV)
-    want_y = torch.zeros(n_rows, cout, dtype=torch.float64, device=DEV)
-    want_dx = torch.zeros(n_rows, cin, dtype=torch.float64, device=DEV)
-    pos_o = torch.full((M_out,), -1, dtype=torch.long, device=DEV)
-    pos_o[rows_o] = torch.arange(n_rows, device=DEV)           # duplicates: the last position wins; handled below
-    pos_i = torch.full((M,), -1, dtype=torch.long, device=DEV)
-    pos_i[rows_i] = torch.arange(n_rows, device=DEV)
-    dw_checked = 0
-    for k, (pi, po) in enumerate(pairs):
-        pi_d, po_d = torch.from_numpy(np.asarray(pi)).to(DEV), torch.from_numpy(np.asarray(po)).to(DEV)
-        sel = pos_o[po_d] >= 0
-        want_y.index_add_(0, pos_o[po_d[sel]], xd[pi_d[sel]] @ W[k])
-        sel = pos_i[pi_d] >= 0
-        want_dx.index_add_(0, pos_i[pi_d[sel]], gyd[po_d[sel]] @ W[k].t())
-        if k in (0, K // 2):
-            dw = xd[pi_d].t() @ gyd[po_d]
-            got = mod.weight.grad.view(K, cin, cout)[k].double()
-            assert float((got - dw).abs().max()) <= 1e-5 * max(float(dw.abs().max()), 1.0), f"dW offset {k}"
-            dw_checked += 1
-    assert dw_checked == 2
-    uo, ui = pos_o[rows_o], pos_i[rows_i]                          # the surviving position of every sampled row
-    sy, sx = float(want_y.abs().max()), float(want_dx.abs().max())
-    assert float((y.detach()[rows_o].double() - want_y[uo]).abs().max()) <= 1e-5 * max(sy, 1.0), "forward values"
-    assert float((x.grad[rows_i].double() - want_dx[ui]).abs().max()) <= 1e-5 * max(sx, 1.0), "dIn values"
+    W = mod.weight.detach().view(K, cin, cout)
+    rows_o = torch.randint(0, M_out, (n_rows,), generator=g).unique().to(DEV)
+    rows_i = torch.randint(0, M_in, (n_rows,), generator=g).unique().to(DEV)
+    want_y = conv_ref.rows(x, W, pairs_d, M_out, rows_o)
+    want_dx = conv_ref.rows(gy, W.transpose(1, 2), conv_ref.swap(pairs_d), M_in, rows_i)
+    want_dw = conv_ref.dw(x, gy, pairs_d)
+    try:
+        for hint in HINTS:
+            _n.check(lib.wsis_hint_batch_rows(hint), "hint")
+            xg = x.clone().requires_grad_(True)
+            mod.weight.grad = None
+            out = mod(make_input(xg))
+            y = out.features
+            assert y.shape == (M_out, cout)
+            if out_idx is not None:      # strided conv: output rows in ascending linear index = the oracle's order
+                assert np.array_equal(out.indices.cpu().numpy(), np.asarray(out_idx, dtype=np.int32))
+            y.backward(gy)
+            sy, sx = float(want_y.abs().max()), float(want_dx.abs().max())
+            assert float((y.detach()[rows_o].double() - want_y).abs().max()) <= 1e-5 * max(sy, 1.0), "forward values"
+            assert float((xg.grad[rows_i].double() - want_dx).abs().max()) <= 1e-5 * max(sx, 1.0), "dIn values"
+            what = f"{kind} {cin}->{cout} M_out={M_out} hint={hint}"
+            err, bound, err_drop = conv_ref.check_dw(mod.weight.grad.view(K, cin, cout), x, gy, pairs_d, 1e-5, what,
+                                                     want=want_dw)
+            print(f"{what}: dW all {K} offsets err {err:.2e} <= {bound:.2e}; one pair removed {err_drop:.2e}")
+    finally:
+        _n.check(lib.wsis_hint_batch_rows(0), "hint")
 
 
 def _level_indices(batch, level):
@@ -256,10 +278,17 @@ def test_c2_conv_values_against_oracle_tables(c2_batch, level, cin, cout):
     _oracle_rows_check(idx, shape, cin, cout, 4096, 100 + level)
 
 
-@pytest.mark.parametrize("level,cin,cout", [(0, 32, 64), (2, 96, 128)])
+@pytest.mark.parametrize("level,cin,cout", [(0, 32, 64), (1, 64, 96), (2, 96, 128), (3, 128, 160)])
 def test_c2_strided_conv_values_against_oracle_tables(c2_batch, level, cin, cout):
     idx, shape = _level_indices(c2_batch, level)
     _oracle_rows_check(idx, shape, cin, cout, 4096, 200 + level, kind="down")
+
+
+@pytest.mark.parametrize("level,cin,cout", [(0, 64, 32), (1, 96, 64), (2, 128, 96), (3, 160, 128)])
+def test_c2_inverse_conv_values_against_oracle_tables(c2_batch, level, cin, cout):
+    """the four SparseInverseConv3d of the UNet (level + 1 -> level) on the transposed tables nbr_up_p / order_up"""
+    idx, shape = _level_indices(c2_batch, level)
+    _oracle_rows_check(idx, shape, cin, cout, 4096, 500 + level, kind="inverse")
 
 
 @pytest.mark.parametrize("level,cin,cout", [(0, 32, 32), (1, 64, 64)])
