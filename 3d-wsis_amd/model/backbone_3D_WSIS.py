@@ -127,7 +127,12 @@ class Network(nn.Module):
         # SyncBatchNorm keeps the native executor: the op list is issued in parts around the statistics exchange of every
         # layer (unet_native._BnSync; WSIS_SYNC_BN_NATIVE=0: the per-module walk with _SyncBatchNormReLU)
         sync_native = sync_bn and os.environ.get("WSIS_SYNC_BN_NATIVE", "1") != "0"
-        if input.features.is_cuda and os.environ.get("WSIS_NATIVE_UNET", "1") != "0" and (not sync_bn or sync_native):
+        # the recorded native pass is fp32 only: 16-bit features or an active autocast region walk the modules, whose
+        # sparse convolutions then compute in 16 bits (spconv.ops.compute_dtype)
+        fp32_pass = input.features.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+        self.last_pass = "native" if (input.features.is_cuda and fp32_pass and os.environ.get("WSIS_NATIVE_UNET", "1") != "0"
+                                      and (not sync_bn or sync_native)) else "modules"
+        if self.last_pass == "native":
             # input_conv -> unet -> output_layer recorded as an op list and issued by one native call per pass
             # (model/unet_native.py); WSIS_NATIVE_UNET=0 walks the modules instead (same kernels, same results)
             import unet_native

@@ -13,6 +13,9 @@ so both paths agree bit for bit; what disappears is ~450 Python-dispatched autog
 Activations live in one arena per pass (bump allocation, nothing is freed before the backward: 288 GB of HBM make
 rematerialisation pointless at these sizes), parameter gradients densely in one flat buffer whose views become
 ``p.grad`` (and which ``parallel.GradSync`` all-reduces in place).
+
+The op list is fp32 only: ``Network.forward`` takes this pass for fp32 features outside autocast, and walks the modules
+(16-bit sparse convolutions, spconv.ops.compute_dtype) for 16-bit features or under ``torch.autocast``.
 """
 import os
 

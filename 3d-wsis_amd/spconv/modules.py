@@ -95,8 +95,10 @@ class SparseSequential(SparseModule):
                     # peephole: BatchNorm1d followed by ReLU runs as ONE fused HIP operator (same module
                     # objects, parameters and state-dict; only the execution is fused)
                     nxt = mods[i + 1] if i + 1 < len(mods) else None
+                    # (fp32 features only: the fused operator computes and returns fp32; 16-bit features run the
+                    # torch modules, whose BatchNorm1d keeps fp32 statistics)
                     if (isinstance(module, nn.BatchNorm1d) and type(nxt) is nn.ReLU and input.features.is_cuda
-                            and _fuse_bn_relu()):
+                            and input.features.dtype == torch.float32 and _fuse_bn_relu()):
                         import wsis_ops
                         input.features = wsis_ops.batch_norm_relu(input.features, module, relu=True)
                         i += 1

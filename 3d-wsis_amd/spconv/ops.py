@@ -563,16 +563,157 @@ def _dw(X, nbr, order, dY, K, Cin, Cout):
     return dW
 
 
+# ---- 16-bit compute path (csrc/spconv_lp.hip): bf16 / fp16 operands, fp32 accumulation -------------------------------
+
+_LP_DTYPES = {torch.bfloat16: 0, torch.float16: 1}
+
+# products (forward, dIn or dW) of the 16-bit path that ran outside the 16-bit kernels' domain (channel counts that are
+# not multiples of 32, such as the 6 -> 32 input convolution): widened to fp32, run by the fp32 kernels, rounded once
+LOWP_FALLBACKS = 0
+
+
+def compute_dtype(features):
+    """the dtype a sparse convolution of ``features`` computes in: bf16 / fp16 features -> that dtype; fp32 features in an
+    active CUDA autocast region with a 16-bit dtype -> the autocast dtype; anything else -> None (the fp32 path)"""
+    if features.dtype in _LP_DTYPES:
+        return features.dtype
+    if features.dtype == torch.float32 and features.is_cuda and torch.is_autocast_enabled("cuda"):
+        dt = torch.get_autocast_dtype("cuda")
+        if dt in _LP_DTYPES:
+            return dt
+    return None
+
+
+def lp_supported(K, Cin, Cout, rows):
+    """the 16-bit kernels take this product: channel domain of wsis_spconv_lp_supported and a gathered tensor of `rows`
+    x Cin 16-bit values below 2 GiB (32-bit gather offsets)"""
+    return bool(_n.hip().wsis_spconv_lp_supported(K, Cin, Cout)) and rows * Cin * 2 < (1 << 31)
+
+
+def _lp_fallback():
+    global LOWP_FALLBACKS
+    LOWP_FALLBACKS += 1
+
+
+def _aligned(t):
+    """contiguous with a 16-byte aligned base (the kernels' 16-byte row loads)"""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _weight_lp(W, dtype, transpose, flip):
+    """fp32 W [K,Cin,Cout] -> 16-bit [K,Cout,Cin] (transpose) or [K,Cin,Cout], slice K-1-k when ``flip``"""
+    K, Cin, Cout = W.shape
+    out = torch.empty((K, Cout, Cin) if transpose else (K, Cin, Cout), dtype=dtype, device=W.device)
+    _n.check(_n.hip().wsis_weight_cast_lp(_n.ptr(W), _n.ptr(out), K, Cin, Cout, int(transpose), int(flip),
+                                          _LP_DTYPES[dtype], _n.stream_ptr()), "weight_cast_lp")
+    return out
+
+
+def _conv_lp(X, nbr, order, WT, flip, bias, M_out):
+    """16-bit out[r] = sum_k X[nbr[k][r]] @ W[k] with the B^T weights WT [K,Cout,Cin] (slice K-1-k when ``flip``)"""
+    K, Cout, Cin = WT.shape
+    out = torch.empty((M_out, Cout), dtype=X.dtype, device=X.device)
+    lib = _n.hip()
+    ws_bytes = lib.wsis_spconv_fwd_lp_workspace_bytes(M_out, K, Cin, Cout)
+    _n.check(lib.wsis_spconv_fwd_lp(_n.ptr(X), _n.ptr(nbr), _n.ptr(order), _n.ptr(WT), int(flip), _n.ptr(bias),
+                                    _n.ptr(out), X.shape[0], M_out, K, Cin, Cout, _LP_DTYPES[X.dtype], None, ws_bytes,
+                                    _n.stream_ptr()), "spconv_fwd_lp")
+    return out
+
+
+def _dw_lp(X, nbr, order, dY, K, Cin, Cout):
+    """fp32 dW [K,Cin,Cout] = sum_r X[nbr[k][r]]^T (x) dY[r] of 16-bit X and dY"""
+    lib = _n.hip()
+    M_out = dY.shape[0]
+    ws_bytes = lib.wsis_spconv_dw_lp_workspace_bytes(M_out, K, Cin, Cout)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device) if ws_bytes > 256 else None
+    dW = torch.empty((K, Cin, Cout), dtype=torch.float32, device=X.device)
+    _n.check(lib.wsis_spconv_dw_lp(_n.ptr(X), _n.ptr(nbr), _n.ptr(order), _n.ptr(dY), _n.ptr(dW), X.shape[0], M_out, K,
+                                   Cin, Cout, _LP_DTYPES[X.dtype], _n.ptr(ws), ws_bytes, _n.stream_ptr()), "spconv_dw_lp")
+    return dW
+
+
+def _fwd_fp32(X, nbr, order, W, b, M_out):
+    """the fp32 forward product as SparseConvFunction's fp32 path runs it"""
+    K, Cin, Cout = W.shape
+    if _use_fwd2(K, Cin, Cout, X.shape[0]):
+        return _conv_t(X, nbr, order, _weight_t(W, 0), 0, b, None, M_out)
+    return _conv(X, nbr, order, W, b, None, M_out)
+
+
+def _din_fp32(dY, nbr, order, W, flip, M_in):
+    """the fp32 dIn product as SparseConvFunction's fp32 backward runs it"""
+    K, Cin, Cout = W.shape
+    if _use_fwd2(K, Cout, Cin, dY.shape[0]):
+        return _conv_t(dY, nbr, order, W, flip, None, None, M_in)
+    return _conv(dY, nbr, order, _weight_t(W, flip), None, None, M_in)
+
+
+def _forward_lp(ctx, features, weight, bias, nbr_f, order_f, nbr_b, order_b, flip, M_out, cd):
+    X = _aligned(features.detach().to(cd))
+    Cin, Cout = weight.shape[-2], weight.shape[-1]
+    W = weight.detach()
+    if W.dtype != torch.float32 or not W.is_contiguous():
+        W = W.contiguous().float()              # the fp32 master copy (autocast) or the widened 16-bit parameter
+    W = W.view(-1, Cin, Cout)
+    K = W.shape[0]
+    b = bias.detach().contiguous().float() if bias is not None else None
+    if lp_supported(K, Cin, Cout, X.shape[0]):
+        out = _conv_lp(X, nbr_f, order_f, _weight_lp(W, cd, 1, 0), 0, b, M_out)
+    else:
+        _lp_fallback()
+        out = _fwd_fp32(X.float(), nbr_f, order_f, W, b, M_out).to(cd)
+    ctx.save_for_backward(X, W)                 # the 16-bit X: what the backward pass reads
+    ctx.aux = (nbr_f, order_f, nbr_b, order_b, flip, weight.shape, bias is not None)
+    ctx.lowp = (cd, features.dtype, weight.dtype, bias.dtype if bias is not None else None)
+    return out
+
+
+def _backward_lp(ctx, grad_out):
+    X, W = ctx.saved_tensors
+    nbr_f, order_f, nbr_b, order_b, flip, wshape, has_bias = ctx.aux
+    cd, in_dtype, w_dtype, b_dtype = ctx.lowp
+    dY = _aligned(grad_out.to(cd))
+    K, Cin, Cout = W.shape
+    dX = dW = db = None
+    if ctx.needs_input_grad[0]:
+        if lp_supported(K, Cout, Cin, dY.shape[0]):
+            dX = _conv_lp(dY, nbr_b, order_b, _weight_lp(W, cd, 0, 0), flip, None, X.shape[0])
+        else:
+            _lp_fallback()
+            dX = _din_fp32(dY.float(), nbr_b, order_b, W, flip, X.shape[0]).to(cd)
+        dX = dX.to(in_dtype)
+    if ctx.needs_input_grad[1]:
+        if lp_supported(K, Cin, Cout, X.shape[0]) and dY.shape[0] * Cout * 2 < (1 << 31):
+            dW = _dw_lp(X, nbr_f, order_f, dY, K, Cin, Cout)
+        else:
+            _lp_fallback()
+            dW = _dw(X.float(), nbr_f, order_f, dY.float(), K, Cin, Cout)
+        dW = dW.view(wshape).to(w_dtype)
+    if has_bias and ctx.needs_input_grad[2]:
+        db = dY.float().sum(0).to(b_dtype)
+    return dX, dW, db, None, None, None, None, None, None
+
+
 class SparseConvFunction(Function):
     """features [M_in,Cin], weight [k0,k1,k2,Cin,Cout] -> [M_out,Cout].
 
     nbr_f/order_f: PACKED gather table + tile order of the forward pass (rows = outputs);
     nbr_b/order_b: packed gather table + tile order of the dIn pass (rows = inputs);
-    flip: subm dIn uses W[K-1-k]^T."""
+    flip: subm dIn uses W[K-1-k]^T.
+
+    Compute dtype (``compute_dtype``): bf16 / fp16 features, or fp32 features under CUDA autocast with a 16-bit dtype,
+    run the 16-bit kernels (fp32 accumulation; output in that dtype, 16-bit X saved for backward, dX in the features'
+    dtype, dW fp32 returned in the weight's dtype); everything else runs the fp32 kernels as before."""
 
     @staticmethod
     def forward(ctx, features, weight, bias, nbr_f, order_f, nbr_b, order_b, flip, M_out):
         _n.require_cuda(features, weight)
+        cd = compute_dtype(features)
+        ctx.lowp = None
+        if cd is not None:
+            return _forward_lp(ctx, features, weight, bias, nbr_f, order_f, nbr_b, order_b, flip, M_out, cd)
         X = features if (features.dtype == torch.float32 and features.is_contiguous()) else features.contiguous().float()
         Cin, Cout = weight.shape[-2], weight.shape[-1]
         W = weight.detach()
@@ -590,6 +731,8 @@ class SparseConvFunction(Function):
 
     @staticmethod
     def backward(ctx, grad_out):
+        if ctx.lowp is not None:
+            return _backward_lp(ctx, grad_out)
         X, W = ctx.saved_tensors
         nbr_f, order_f, nbr_b, order_b, flip, wshape, has_bias = ctx.aux
         dY = grad_out if (grad_out.dtype == torch.float32 and grad_out.is_contiguous()) else grad_out.contiguous().float()

@@ -88,6 +88,12 @@ _HIP_SIGS = {
     "wsis_weight_transpose": (I32, [P, P, I32, I32, I32, I32, P]),
     "wsis_spconv_dw_workspace_bytes": (I64, [I64, I32, I32, I32]),
     "wsis_spconv_dw": (I32, [P, P, P, P, P, I64, I64, I32, I32, I32, P, I64, P]),
+    "wsis_spconv_lp_supported": (I32, [I32, I32, I32]),
+    "wsis_spconv_fwd_lp_workspace_bytes": (I64, [I64, I32, I32, I32]),
+    "wsis_spconv_fwd_lp": (I32, [P, P, P, P, I32, P, P, I64, I64, I32, I32, I32, I32, P, I64, P]),
+    "wsis_spconv_dw_lp_workspace_bytes": (I64, [I64, I32, I32, I32]),
+    "wsis_spconv_dw_lp": (I32, [P, P, P, P, P, I64, I64, I32, I32, I32, I32, P, I64, P]),
+    "wsis_weight_cast_lp": (I32, [P, P, I32, I32, I32, I32, I32, I32, P]),
     "wsis_spconv_dw_bn_supported": (I32, [I32, I32, I32]),
     "wsis_spconv_dw_bn_workspace_bytes": (I64, [I64, I32, I32, I32]),
     "wsis_spconv_dw_bn": (I32, [P, P, P, P, P, F32, I32, P, P, I32, P, P, I64, I64, I32, I32, I32, P, I64, P]),

@@ -754,7 +754,9 @@ class _TallLinear(Function):
 
 def tall_linear(x, linear):
     # rows from which the row-split dW reduction beats the one-workgroup GEMM (measured at 2.3 k rows: 15 -> 7 us)
-    if not x.is_cuda or x.dim() != 2 or x.shape[0] < _TALL_MIN_ROWS or x.dtype != torch.float32:
+    # (under CUDA autocast the module runs: it follows the autocast dtype, the fp32 operator does not)
+    if (not x.is_cuda or x.dim() != 2 or x.shape[0] < _TALL_MIN_ROWS or x.dtype != torch.float32
+            or torch.is_autocast_enabled("cuda")):
         return linear(x)
     return _TallLinear.apply(x, linear.weight, linear.bias)
 

@@ -288,6 +288,35 @@ int wsis_spconv_dw(const float* d_X, const int32_t* d_nbr, const int32_t* d_orde
                    float* d_dW, int64_t M_in, int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, void* d_ws,
                    int64_t ws_bytes, void* stream);
 
+/* ---- 16-bit sparse convolution (bf16 / fp16 operands, fp32 accumulation): csrc/spconv_lp.hip --------------------
+ * The same products as wsis_spconv_fwd_t / wsis_spconv_dw for features and weights in 16 bits -- what upstream spconv
+ * runs for half features under mixed precision [UPSTREAM spconv indiceConv / indiceConvBackward with fp16 tensors].
+ * dtype: 0 = bf16, 1 = fp16; every 16-bit buffer holds that type.  Domain: Cin and Cout multiples of 32, at most 512,
+ * any K, gathered tensors below 2 GiB (32-bit gather offsets); outside it the caller widens to fp32. */
+int32_t wsis_spconv_lp_supported(int32_t K, int32_t Cin, int32_t Cout);
+/* out[r] = sum_k X[nbr[k][r]] @ W[k] with 16-bit X [M_in, Cin] and B^T weights d_WT [K, Cout, Cin] (slice K-1-k when
+ * flip: the conventions of wsis_spconv_fwd_t, which it replaces at the same call sites for 16-bit features:
+ * sparse_unet3d.py:130,261,292 forward, SURVEY a11 dIn with d_WT = the plain 16-bit cast of the weight).  d_nbr / d_order
+ * as for wsis_spconv_fwd; K == 1 with d_nbr == NULL is the dense 1x1 shortcut; d_bias optional fp32 [Cout].  fp32
+ * accumulators, each output element rounded to 16 bits once; the order of additions of an output row depends on the
+ * offset index only (bit-reproducible).  No offset split: the workspace query returns a minimal size. */
+int64_t wsis_spconv_fwd_lp_workspace_bytes(int64_t M_out, int32_t K, int32_t Cin, int32_t Cout);
+int wsis_spconv_fwd_lp(const void* d_X, const int32_t* d_nbr, const int32_t* d_order, const void* d_WT, int32_t flip,
+                       const float* d_bias, void* d_out, int64_t M_in, int64_t M_out, int32_t K, int32_t Cin,
+                       int32_t Cout, int32_t dtype, void* d_ws, int64_t ws_bytes, void* stream);
+/* dW[k] = sum_r X[nbr[k][r]]^T (x) dY[r] with 16-bit X [M_in, Cin] and dY [M_out, Cout] -> fp32 d_dW [K, Cin, Cout]
+ * (overwritten): the 16-bit form of wsis_spconv_dw [UPSTREAM spconv indiceConvBackward, filter gradient].  Partial slabs
+ * per row chunk in d_ws, added in chunk order: no atomics, bit-reproducible. */
+int64_t wsis_spconv_dw_lp_workspace_bytes(int64_t M_out, int32_t K, int32_t Cin, int32_t Cout);
+int wsis_spconv_dw_lp(const void* d_X, const int32_t* d_nbr, const int32_t* d_order, const void* d_dY, float* d_dW,
+                      int64_t M_in, int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* d_ws,
+                      int64_t ws_bytes, void* stream);
+/* fp32 W [K, Cin, Cout] -> 16-bit d_out, rounded to nearest even (NaN stays NaN): [K, Cout, Cin] = W[k]^T when transpose
+ * (the d_WT of the forward pass), [K, Cin, Cout] otherwise (the dIn operand); slice k goes to K-1-k when flip.  The
+ * 16-bit counterpart of wsis_weight_transpose. */
+int wsis_weight_cast_lp(const float* d_W, void* d_out, int32_t K, int32_t Cin, int32_t Cout, int32_t transpose,
+                        int32_t flip, int32_t dtype, void* stream);
+
 /* The same weight gradient for a convolution whose INPUT is BatchNorm(+ReLU)(d_X) applied on the fly (the activation
  * relu(bn(x)) of sparse_unet3d.py:128-137 is never materialised: the forward pass normalises the gathered rows as it
  * reads them, wsis_spconv_fwd_f): dW[k] = sum_pairs relu(bn(X[i]))^T (x) dY[o].  "Own rows" form: the slices run over
