@@ -212,25 +212,47 @@ int dw_chunks(int64_t M_out, int K, int Cin, int Cout) {
   return (int)std::max<int64_t>(c, 1);
 }
 
+// the launch plan of both products for a shape: what the launches below run and wsis_spconv_lp_plan reports
+struct LpPlan {
+  int nt, ncg;             // forward / dIn: output tiles of 32 channels per wave, channel groups (grid = blocks)
+  int64_t fwd_blocks;
+  int chunks;              // weight gradient: row chunks (partial slabs), rows per chunk (a multiple of 32)
+  int64_t rows_per_chunk;
+  int nw, groups;          // waves per workgroup, tile groups (grid x)
+  int64_t lds;             // dynamic LDS bytes of the transposed stage
+};
+
+LpPlan lp_plan(int64_t M_out, int K, int Cin, int Cout) {
+  LpPlan p;
+  // output channels per wave: two tiles where they split evenly and the level has rows enough to fill the CUs
+  p.nt = (Cout / 32) % 2 == 0 && ceil_div(M_out, 32) * (Cout / 64) >= 4096 ? 2 : 1;
+  p.ncg = Cout / (32 * p.nt);
+  p.fwd_blocks = ceil_div(ceil_div(M_out, 32), LP_WAVES) * p.ncg;
+  p.chunks = dw_chunks(M_out, K, Cin, Cout);
+  p.rows_per_chunk = ceil_div(ceil_div(M_out, p.chunks), 32) * 32;
+  const int ntiles = (Cin / 32) * (Cout / 32);
+  p.nw = std::min(LP_WAVES, ntiles);
+  p.groups = (int)ceil_div(ntiles, p.nw * DW_TPW);
+  p.lds = (int64_t)(Cin + Cout) * DW_PAD * 2;
+  return p;
+}
+
 template <typename T, int NT>
 void launch_fwd(const void* X, const int32_t* nbr, const int32_t* order, const void* WT, int flip, const float* bias,
-                void* out, int64_t M_out, int K, int Cin, int Cout, hipStream_t st) {
-  const int ncg = Cout / (32 * NT);
-  const int64_t blocks = ceil_div(ceil_div(M_out, 32), LP_WAVES) * ncg;
-  hipLaunchKernelGGL((spconv_lp_fwd_kernel<T, NT>), dim3((unsigned)blocks), dim3(64 * LP_WAVES), 0, st,
+                void* out, int64_t M_out, int K, int Cin, int Cout, const LpPlan& p, hipStream_t st) {
+  hipLaunchKernelGGL((spconv_lp_fwd_kernel<T, NT>), dim3((unsigned)p.fwd_blocks), dim3(64 * LP_WAVES), 0, st,
                      static_cast<const T*>(X), nbr, order, static_cast<const T*>(WT), flip, bias, static_cast<T*>(out),
-                     M_out, K, Cin, Cout, ncg);
+                     M_out, K, Cin, Cout, p.ncg);
 }
 
 template <typename T>
 void launch_fwd_t(const void* X, const int32_t* nbr, const int32_t* order, const void* WT, int flip, const float* bias,
                   void* out, int64_t M_out, int K, int Cin, int Cout, hipStream_t st) {
-  // output channels per wave: two tiles where they split evenly and the level has rows enough to fill the CUs
-  const bool two = (Cout / 32) % 2 == 0 && ceil_div(M_out, 32) * (Cout / 64) >= 4096;
-  if (two)
-    launch_fwd<T, 2>(X, nbr, order, WT, flip, bias, out, M_out, K, Cin, Cout, st);
+  const LpPlan p = lp_plan(M_out, K, Cin, Cout);
+  if (p.nt == 2)
+    launch_fwd<T, 2>(X, nbr, order, WT, flip, bias, out, M_out, K, Cin, Cout, p, st);
   else
-    launch_fwd<T, 1>(X, nbr, order, WT, flip, bias, out, M_out, K, Cin, Cout, st);
+    launch_fwd<T, 1>(X, nbr, order, WT, flip, bias, out, M_out, K, Cin, Cout, p, st);
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -241,6 +263,17 @@ int32_t wsis_spconv_lp_supported(int32_t K, int32_t Cin, int32_t Cout) {
   return (K >= 1 && Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0 && Cin <= LP_MAX_C && Cout <= LP_MAX_C)
              ? 1
              : 0;
+}
+
+int32_t wsis_spconv_lp_plan(int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, int32_t* out) {
+  WSIS_REQUIRE(out, "null pointer");
+  WSIS_REQUIRE(M_out >= 1 && M_out < (int64_t)1 << 31, "M_out must be in [1, 2^31)");
+  WSIS_REQUIRE(wsis_spconv_lp_supported(K, Cin, Cout), "needs channel counts that are multiples of 32, at most 512");
+  const LpPlan p = lp_plan(M_out, K, Cin, Cout);
+  const int64_t v[8] = {p.nt, p.ncg, p.fwd_blocks, p.chunks, p.rows_per_chunk, p.nw, p.groups, p.lds};
+  for (int i = 0; i < 8; ++i) WSIS_REQUIRE(v[i] <= INT32_MAX, "a plan value exceeds int32");
+  for (int i = 0; i < 8; ++i) out[i] = (int32_t)v[i];
+  return WSIS_OK;
 }
 
 int64_t wsis_spconv_fwd_lp_workspace_bytes(int64_t M_out, int32_t K, int32_t Cin, int32_t Cout) {
@@ -295,25 +328,22 @@ int wsis_spconv_dw_lp(const void* d_X, const int32_t* d_nbr, const int32_t* d_or
   WSIS_REQUIRE(M_out < (int64_t)1 << 31 && M_in < (int64_t)1 << 31, "row count exceeds int32");
   WSIS_REQUIRE(M_in * Cin * 2 < (int64_t)1 << 31, "input tensor of 2 GiB or more (32-bit gather offsets)");
   WSIS_REQUIRE(aligned16(d_X) && aligned16(d_dY), "X and dY must be 16-byte aligned");
-  const int chunks = dw_chunks(M_out, K, Cin, Cout);
-  WSIS_REQUIRE(ws_bytes >= wsis_spconv_dw_lp_workspace_bytes(M_out, K, Cin, Cout) && (chunks == 1 || d_ws),
+  const LpPlan p = lp_plan(M_out, K, Cin, Cout);
+  WSIS_REQUIRE(ws_bytes >= wsis_spconv_dw_lp_workspace_bytes(M_out, K, Cin, Cout) && (p.chunks == 1 || d_ws),
                "workspace too small");
-  const int64_t rpc = ceil_div(ceil_div(M_out, chunks), 32) * 32;
-  const int ntiles = (Cin / 32) * (Cout / 32);
-  const int nw = std::min(LP_WAVES, ntiles);
-  const int groups = (int)ceil_div(ntiles, nw * DW_TPW);
-  float* slab = chunks > 1 ? static_cast<float*>(d_ws) : d_dW;
-  const size_t lds = (size_t)(Cin + Cout) * DW_PAD * 2;
-  const dim3 grid(groups, chunks, K);
+  float* slab = p.chunks > 1 ? static_cast<float*>(d_ws) : d_dW;
+  const dim3 grid(p.groups, p.chunks, K);
   if (dtype == 0)
-    hipLaunchKernelGGL(spconv_lp_dw_kernel<__bf16>, grid, dim3(64 * nw), lds, st, static_cast<const __bf16*>(d_X),
-                       d_nbr, d_order, static_cast<const __bf16*>(d_dY), slab, M_out, K, Cin, Cout, rpc);
+    hipLaunchKernelGGL(spconv_lp_dw_kernel<__bf16>, grid, dim3(64 * p.nw), (size_t)p.lds, st,
+                       static_cast<const __bf16*>(d_X), d_nbr, d_order, static_cast<const __bf16*>(d_dY), slab, M_out,
+                       K, Cin, Cout, p.rows_per_chunk);
   else
-    hipLaunchKernelGGL(spconv_lp_dw_kernel<_Float16>, grid, dim3(64 * nw), lds, st, static_cast<const _Float16*>(d_X),
-                       d_nbr, d_order, static_cast<const _Float16*>(d_dY), slab, M_out, K, Cin, Cout, rpc);
+    hipLaunchKernelGGL(spconv_lp_dw_kernel<_Float16>, grid, dim3(64 * p.nw), (size_t)p.lds, st,
+                       static_cast<const _Float16*>(d_X), d_nbr, d_order, static_cast<const _Float16*>(d_dY), slab,
+                       M_out, K, Cin, Cout, p.rows_per_chunk);
   WSIS_LAUNCH_CHECK();
-  if (chunks > 1) {
-    hipLaunchKernelGGL(spconv_lp_dw_sum_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, slab, d_dW, n, chunks);
+  if (p.chunks > 1) {
+    hipLaunchKernelGGL(spconv_lp_dw_sum_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, slab, d_dW, n, p.chunks);
     WSIS_LAUNCH_CHECK();
   }
   return WSIS_OK;

@@ -89,6 +89,7 @@ _HIP_SIGS = {
     "wsis_spconv_dw_workspace_bytes": (I64, [I64, I32, I32, I32]),
     "wsis_spconv_dw": (I32, [P, P, P, P, P, I64, I64, I32, I32, I32, P, I64, P]),
     "wsis_spconv_lp_supported": (I32, [I32, I32, I32]),
+    "wsis_spconv_lp_plan": (I32, [I64, I32, I32, I32, P]),
     "wsis_spconv_fwd_lp_workspace_bytes": (I64, [I64, I32, I32, I32]),
     "wsis_spconv_fwd_lp": (I32, [P, P, P, P, I32, P, P, I64, I64, I32, I32, I32, I32, P, I64, P]),
     "wsis_spconv_dw_lp_workspace_bytes": (I64, [I64, I32, I32, I32]),

@@ -294,6 +294,15 @@ int wsis_spconv_dw(const float* d_X, const int32_t* d_nbr, const int32_t* d_orde
  * dtype: 0 = bf16, 1 = fp16; every 16-bit buffer holds that type.  Domain: Cin and Cout multiples of 32, at most 512,
  * any K, gathered tensors below 2 GiB (32-bit gather offsets); outside it the caller widens to fp32. */
 int32_t wsis_spconv_lp_supported(int32_t K, int32_t Cin, int32_t Cout);
+/* The launch plan the two products below run for this shape (host-only, reads nothing on the device; the launches
+ * compute it with the same helper).  M_out = output rows of wsis_spconv_fwd_lp, or dY rows of wsis_spconv_dw_lp.
+ * out[8]: forward / dIn  [0] NT (32-column output tiles per wave: 2 when Cout / 32 is even and
+ *                            ceil(M_out / 32) * Cout / 64 >= 4096, else 1), [1] ncg = Cout / (32 NT) channel groups,
+ *                            [2] forward blocks;
+ *         weight gradient [3] row chunks (partial slabs; 1 = written straight into dW), [4] rows per chunk (a
+ *                            multiple of 32), [5] waves per workgroup, [6] tile groups, [7] LDS bytes.
+ * Returns 0, or nonzero for M_out outside [1, 2^31), a shape outside wsis_spconv_lp_supported or a NULL out. */
+int32_t wsis_spconv_lp_plan(int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, int32_t* out);
 /* out[r] = sum_k X[nbr[k][r]] @ W[k] with 16-bit X [M_in, Cin] and B^T weights d_WT [K, Cout, Cin] (slice K-1-k when
  * flip: the conventions of wsis_spconv_fwd_t, which it replaces at the same call sites for 16-bit features:
  * sparse_unet3d.py:130,261,292 forward, SURVEY a11 dIn with d_WT = the plain 16-bit cast of the weight).  d_nbr / d_order
