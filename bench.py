@@ -10,12 +10,16 @@ N > 1 (BASELINE.json configs[4], "C5"): --scenes-per-gpu defaults to 4 (batch 32
 rank, no data-path collective, weak scaling.  `python bench.py --gpus N` without a launcher starts the N ranks itself
 (a torch.distributed.run child, before anything touches the GPU) and fails non-zero if the RCCL world is not N.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps, writes --dump-outputs and
+prints the line; `roofline` and `cpu_baseline` are null in it.  Everything else the benchmark measures runs only with
+--full, after the timed steps (--profile-steps, --no-stages and --no-cpu-baseline trim it), and fills in:
   roofline      -- dominant kernel family (the forward / dIn launches of the 49 sparse convs: spconv_fwd2_kernel,
                    spconv_in_kernel for the 6-channel input conv): algorithmic gather/scatter bytes (P*(Cin+Cout)*4 + P*8 per launch,
                    SURVEY 8d) / HIP-event time of those launches, against the 8 TB/s HBM peak.
   cpu_baseline  -- the oracle (torch-CPU restatement mirroring upstream's gather -> mm -> scatter-add) timed on
                    this box's host cores on the same scene (rank 0, N = 1 only).
+  side numbers  -- copy / triad bandwidth, optimizer step, clustering, propagation, batch assembly, C3 / C4 (N = 1), and
+                   at N > 1 the exchange-free `scaling_baseline` of the line's per-GPU batch (taken before the timed steps).
 """
 import argparse
 import importlib
@@ -68,9 +72,13 @@ def parse():
                          "(spconv.ops.RulebookPipeline; measured neutral: 69.0 / 69.3 vs 68.9 / 69.1 scenes/s)")
     ap.add_argument("--prefetch", action="store_true",
                     help="build the next step's rulebooks from a helper thread (measured slower: GIL contention)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline / per-kernel figures, side measurements, other configurations, "
+                         "the CPU baseline and (N > 1) the exchange-free scaling baseline")
     ap.add_argument("--profile-steps", type=int, default=3,
-                    help="extra event-instrumented steps for the roofline (>= 3: per launch the median of its occurrences)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: extra event-instrumented steps for the roofline (>= 3: per launch the median of its "
+                         "occurrences)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-iters", type=int, default=5)
     ap.add_argument("--cpu-warmup", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=8)
@@ -82,7 +90,7 @@ def parse():
                          "falling for the first few hundred steps of a process (13.1 ms after 3 passes, 12.0 ms after "
                          "300 or 600, DESIGN section 5); a training run sits in that steady state")
     ap.add_argument("--no-stages", action="store_true",
-                    help="skip the side measurements (copy/triad bandwidth, optimizer step, clustering stage)")
+                    help="--full: skip the side measurements (copy/triad bandwidth, optimizer step, clustering stage)")
     ap.add_argument("--scene-seed", type=int, default=1)
     ap.add_argument("--scenes-per-gpu", type=int, default=0,
                     help="scenes per rank and step; default 1 at --gpus 1 (C2), 4 at --gpus > 1 (C5: batch 32 / 8 GPUs)")
@@ -673,9 +681,10 @@ def main():
     # `spg` scenes per GPU, and a step of 4 scenes runs ~1.5x the scenes/s of a step of one on the same GPU.  So every
     # line carries `scaling_baseline`: what ONE GPU does with this line's per-GPU batch and no gradient exchange --
     # measured here, in this process, on this rank's own batch (N > 1), or taken from the 4-scene side measurement of
-    # the default run (N = 1).  Efficiency of a line = value / (n_gpus x scaling_baseline.scenes_per_s).
+    # the default run (N = 1).  Efficiency of a line = value / (n_gpus x scaling_baseline.scenes_per_s).  Both come with
+    # --full; without it an N > 1 line carries none and an N = 1 line its own figure.
     local_base = None
-    if use_dist and grad_sync is not None:
+    if args.full and use_dist and grad_sync is not None:
         nb = max(5, min(20, args.steps))
         # Exchange REALLY off for these steps: besides grad_sync=None, the hook the native UNet backward calls for the
         # early half-exchange is unhooked (left armed it would start an all-reduce of half the flat buffer on the
@@ -720,7 +729,8 @@ def main():
         if prog is not None:
             prog.overlap = saved_hook
         assert grad_sync._early is None, "an early exchange was issued during the exchange-off baseline"
-        for _ in range(2):      # back to the timed configuration
+    if use_dist and grad_sync is not None:
+        for _ in range(2):      # back to the timed configuration (a plain run takes these steps too: same weights in both)
             step()
 
     fence()
@@ -738,11 +748,11 @@ def main():
     if args.dump_outputs and rank == 0:     # before the instrumented steps below overwrite them
         dump_outputs(args.dump_outputs, loss, ret)
 
-    # ---- roofline of the dominant kernel: event-instrumented extra steps (same inputs, same process) ----
+    # ---- --full: roofline of the dominant kernel: event-instrumented extra steps (same inputs, same process) ----
     roof = None
     extra = {}
     summ, summ_ov = {}, {}
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         # per-kernel durations are only a property of the kernel when it runs alone: the instrumented steps keep the
         # weight-gradient launches on the main stream (in the timed region they overlap the dIn launches of
         # spconv_fwd_kernel on a side stream, which stretches both -- good for the step, meaningless per kernel).
@@ -816,13 +826,13 @@ def main():
                                "ms_per_step": round(bno["ms"] / args.profile_steps, 3),
                                "ops_per_step": bno["launches"] // args.profile_steps}
 
-    if rank == 0 and world == 1 and not args.no_stages:
+    if args.full and rank == 0 and world == 1 and not args.no_stages:
         extra.update(side_measurements(harness, optimizer, device, args))
         if roof and extra.get("measured_copy_GBs"):       # the same bytes against what a device copy reaches here
             roof["frac_vs_measured_copy"] = round(roof["achieved"] / extra["measured_copy_GBs"], 4)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(int(batch_host["voxel_locs"].shape[0]), args) if spg == 1 else None
 
     # the JSON line must be the LAST thing on stdout: anything a library printed through C stdio (fully buffered on

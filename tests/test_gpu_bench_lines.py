@@ -1,5 +1,6 @@
 """bench.py's documented one-GPU command lines end in ONE parseable JSON line with the contract's keys -- the default
-form and the N = 1 point of the 1 -> 8 series (`--gpus 1 --scenes-per-gpu K`: several scenes per step, no process group).
+form and the N = 1 point of the 1 -> 8 series (`--gpus 1 --scenes-per-gpu K`: several scenes per step, no process group),
+with --full (roofline and side figures) and without it (the headline alone).
 Small rooms, a handful of steps: this checks the plumbing of the line, not its numbers."""
 import json
 import os
@@ -10,7 +11,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--small", "--steps", "2", "--warmup", "1", "--setup-steps", "2", "--no-cpu-baseline", "--no-stages"]
+COMMON = ["--small", "--steps", "2", "--warmup", "1", "--setup-steps", "2"]
+FULL = ["--full", "--no-cpu-baseline", "--no-stages"]
 
 
 def _line(extra):
@@ -26,7 +28,7 @@ def _line(extra):
 
 @pytest.mark.parametrize("extra,spg", [([], 1), (["--gpus", "1", "--scenes-per-gpu", "2"], 2)], ids=["default", "spg2"])
 def test_one_gpu_lines(extra, spg):
-    d = _line(extra)
+    d = _line(FULL + extra)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "scaling_baseline"):
         assert k in d, k
@@ -36,3 +38,16 @@ def test_one_gpu_lines(extra, spg):
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in r, k
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and 0 < r["frac"] < 1
+
+
+def test_plain_line_is_the_headline_alone():
+    """without --full: the same contract keys, no instrumented steps (roofline null), no CPU baseline, no side figures"""
+    d = _line([])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+              "config", "roofline", "cpu_baseline", "scaling_baseline"):
+        assert k in d, k
+    assert d["unit"] == "scenes/s" and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    for k in ("dw_kernel", "bn_ops", "measured_copy_GBs", "c3_batch4_train", "c4_inference", "propagation_stage"):
+        assert k not in d, k

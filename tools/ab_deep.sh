@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for rep in 1 2; do
   for d in 0 1; do
-    WSIS_DEEP=$d python bench.py --no-stages --no-cpu-baseline --steps 40 --warmup 5 --setup-steps 150 2>/dev/null | python -c "
+    WSIS_DEEP=$d python bench.py --full --no-stages --no-cpu-baseline --steps 40 --warmup 5 --setup-steps 150 2>/dev/null | python -c "
 import json,sys
 l=[x for x in sys.stdin.read().split('\n') if x.startswith('{')][-1]
 d=json.loads(l); r=d['roofline']
