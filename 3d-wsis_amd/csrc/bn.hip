@@ -287,11 +287,39 @@ __device__ __forceinline__ float bn_ld_stat(const float* p) {
   return *p;
 }
 
-template <bool COHERENT>
-__device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, const float* mean,
+// four consecutive elements of an fp32 / bf16 / fp16 tensor as fp32 (16-bit values widen exactly), and back: float4 moves
+// 16 bytes, a 16-bit quad 8 bytes (one ushort4); 16-bit stores round to nearest even
+template <typename T>
+__device__ __forceinline__ float4 bn_ld4(const T* p, int64_t t) {
+  if constexpr (sizeof(T) == 4) {
+    return reinterpret_cast<const float4*>(p)[t];
+  } else {
+    const ushort4 u = reinterpret_cast<const ushort4*>(p)[t];
+    return make_float4((float)__builtin_bit_cast(T, u.x), (float)__builtin_bit_cast(T, u.y),
+                       (float)__builtin_bit_cast(T, u.z), (float)__builtin_bit_cast(T, u.w));
+  }
+}
+template <typename T>
+__device__ __forceinline__ void bn_st4(T* p, int64_t t, float4 v) {
+  if constexpr (sizeof(T) == 4) {
+    reinterpret_cast<float4*>(p)[t] = v;
+  } else {
+    ushort4 u;
+    u.x = __builtin_bit_cast(unsigned short, (T)v.x);
+    u.y = __builtin_bit_cast(unsigned short, (T)v.y);
+    u.z = __builtin_bit_cast(unsigned short, (T)v.z);
+    u.w = __builtin_bit_cast(unsigned short, (T)v.w);
+    reinterpret_cast<ushort4*>(p)[t] = u;
+  }
+}
+
+// TI / TO: element types of x and y (float, __bf16 or _Float16).  The arithmetic is fp32 whatever they are: a 16-bit x is
+// widened exactly, y is rounded once at the store -- the 16-bit forms equal the fp32 form on the widened x, rounded.
+template <bool COHERENT, typename TI = float, typename TO = float>
+__device__ __forceinline__ void bn_apply_body(const TI* __restrict__ x, const float* mean,
                                               const float* var, const float* __restrict__ gamma,
                                               const float* __restrict__ beta, float eps, int relu,
-                                              float* __restrict__ y, int64_t M, int C) {
+                                              TO* __restrict__ y, int64_t M, int C) {
   const int64_t total = M * C;
   if ((C & 3) == 0) {
     const int64_t total4 = total >> 2;
@@ -324,19 +352,19 @@ __device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, const
       }
       return make_float4(o[0], o[1], o[2], o[3]);
     };
-    if (fixed_c) {   // two float4 per trip in flight (the launcher rounds the grid so that this branch is taken)
+    if (fixed_c) {   // two quads per trip in flight (the launcher rounds the grid so that this branch is taken)
       for (; t + stride < total4; t += 2 * stride) {
-        const float4 v0 = reinterpret_cast<const float4*>(x)[t];
-        const float4 v1 = reinterpret_cast<const float4*>(x)[t + stride];
-        reinterpret_cast<float4*>(y)[t] = body(v0);
-        reinterpret_cast<float4*>(y)[t + stride] = body(v1);
+        const float4 v0 = bn_ld4(x, t);
+        const float4 v1 = bn_ld4(x, t + stride);
+        bn_st4(y, t, body(v0));
+        bn_st4(y, t + stride, body(v1));
       }
-      if (t < total4) reinterpret_cast<float4*>(y)[t] = body(reinterpret_cast<const float4*>(x)[t]);
+      if (t < total4) bn_st4(y, t, body(bn_ld4(x, t)));
     } else {
       for (; t < total4; t += stride) {
         cg = (unsigned)(t % C4);
         coef(cg);
-        reinterpret_cast<float4*>(y)[t] = body(reinterpret_cast<const float4*>(x)[t]);
+        bn_st4(y, t, body(bn_ld4(x, t)));
       }
     }
   } else {
@@ -344,9 +372,9 @@ __device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, const
          t += (int64_t)gridDim.x * blockDim.x) {
       const int c = (int)(t % C);
       const float sc = (gamma ? gamma[c] : 1.0f) * rsqrtf(bn_ld_stat<COHERENT>(var + c) + eps);
-      float z = __builtin_fmaf(x[t] - bn_ld_stat<COHERENT>(mean + c), sc, beta ? beta[c] : 0.0f);
+      float z = __builtin_fmaf((float)x[t] - bn_ld_stat<COHERENT>(mean + c), sc, beta ? beta[c] : 0.0f);
       if (relu) z = fmaxf(z, 0.0f);
-      y[t] = z;
+      y[t] = (TO)z;
     }
   }
 }
@@ -356,6 +384,26 @@ __global__ void bn_apply_kernel(const float* __restrict__ x, const float* __rest
                                 const float* __restrict__ beta, float eps, int relu, float* __restrict__ y,
                                 int64_t M, int C) {
   bn_apply_body<false>(x, mean, var, gamma, beta, eps, relu, y, M, C);
+}
+
+// the evaluation-mode apply of a 16-bit pass (wsis_bn_apply_lp): 16-bit x, 16-bit or fp32 y
+template <typename TI, typename TO>
+__global__ void bn_apply_lp_kernel(const TI* __restrict__ x, const float* __restrict__ mean,
+                                   const float* __restrict__ var, const float* __restrict__ gamma,
+                                   const float* __restrict__ beta, float eps, int relu, TO* __restrict__ y, int64_t M,
+                                   int C) {
+  bn_apply_body<false, TI, TO>(x, mean, var, gamma, beta, eps, relu, y, M, C);
+}
+
+template <typename TI>
+void launch_bn_apply_lp(const void* x, const float* mean, const float* var, const float* gamma, const float* beta,
+                        float eps, int relu, void* y, int out_fp32, int64_t M, int C, int grid, hipStream_t st) {
+  if (out_fp32)
+    hipLaunchKernelGGL((bn_apply_lp_kernel<TI, float>), dim3(grid), dim3(256), 0, st, static_cast<const TI*>(x), mean,
+                       var, gamma, beta, eps, relu, static_cast<float*>(y), M, C);
+  else
+    hipLaunchKernelGGL((bn_apply_lp_kernel<TI, TI>), dim3(grid), dim3(256), 0, st, static_cast<const TI*>(x), mean, var,
+                       gamma, beta, eps, relu, static_cast<TI*>(y), M, C);
 }
 
 // ---- statistics finish + apply in ONE launch.  The first G * ceil(C/32) workgroups run the chunk stage of
@@ -1371,6 +1419,30 @@ int wsis_bn_apply(const float* d_x, const float* d_mean, const float* d_var, con
   const int grid = bn_apply_grid(work, cw, 2);
   hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, as_stream(stream), d_x, d_mean, d_var,
                      d_gamma, d_beta, eps, relu, d_y, M, C);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+int wsis_bn_apply_lp(const void* d_x, const float* d_mean, const float* d_var, const float* d_gamma,
+                     const float* d_beta, float eps, int32_t relu, void* d_y, int32_t out_fp32, int64_t M, int32_t C,
+                     int32_t dtype, void* stream) {
+  WSIS_REQUIRE(M >= 0 && C >= 1, "bad sizes");
+  WSIS_REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (bf16) or 1 (fp16)");
+  if (M == 0) return WSIS_OK;
+  WSIS_REQUIRE(d_x && d_mean && d_var && d_y, "null pointer");
+  // the grid of wsis_bn_apply: the same walk over the same quads
+  const int64_t work = (C & 3) == 0 ? (M * C) >> 2 : M * C;
+  const int cw = (C & 3) == 0 ? C >> 2 : C;
+  const int grid = bn_apply_grid(work, cw, 2);
+  if ((C & 3) == 0)
+    WSIS_REQUIRE((reinterpret_cast<uintptr_t>(d_x) & 7) == 0 &&
+                     (reinterpret_cast<uintptr_t>(d_y) & (out_fp32 ? 15 : 7)) == 0,
+                 "x and y must be aligned to a quad of elements");
+  hipStream_t st = as_stream(stream);
+  if (dtype == 0)
+    launch_bn_apply_lp<__bf16>(d_x, d_mean, d_var, d_gamma, d_beta, eps, relu, d_y, out_fp32, M, C, grid, st);
+  else
+    launch_bn_apply_lp<_Float16>(d_x, d_mean, d_var, d_gamma, d_beta, eps, relu, d_y, out_fp32, M, C, grid, st);
   WSIS_LAUNCH_CHECK();
   return WSIS_OK;
 }

@@ -73,6 +73,26 @@ __global__ void add_inplace_kernel(float* __restrict__ dst, const float* __restr
     dst[t] += src[t];
 }
 
+// fp32 -> 16-bit, rounded to nearest even (the CAST_LP op: the 16-bit pass's input convolution runs in fp32 and its
+// output is rounded once here).  Four elements per thread where n % 4 == 0 and both bases are aligned to a quad.
+template <typename T>
+__global__ void cast_lp_kernel(const float* __restrict__ x, T* __restrict__ y, int64_t n, int vec) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (vec) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n / 4; t += stride) {
+      const float4 v = reinterpret_cast<const float4*>(x)[t];
+      ushort4 u;
+      u.x = __builtin_bit_cast(unsigned short, (T)v.x);
+      u.y = __builtin_bit_cast(unsigned short, (T)v.y);
+      u.z = __builtin_bit_cast(unsigned short, (T)v.z);
+      u.w = __builtin_bit_cast(unsigned short, (T)v.w);
+      reinterpret_cast<ushort4*>(y)[t] = u;
+    }
+  } else {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += stride) y[t] = (T)x[t];
+  }
+}
+
 inline bool vec4_ok(const wsis_op& op, const void* p0, const void* p1, const void* p2) {
   return (op.Cin % 4 == 0) && (op.Cout % 4 == 0) &&
          ((reinterpret_cast<uintptr_t>(p0) | reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2)) & 15) == 0;
@@ -81,17 +101,19 @@ inline bool vec4_ok(const wsis_op& op, const void* p0, const void* p1, const voi
 // every dIn convolution of a backward pass needs W[k]^T (flipped for submanifold tables): all of them are produced
 // by ONE launch up front instead of one small launch per layer.  One workgroup moves a 32x32 tile of one [Cin, Cout]
 // slice through LDS: reads run along Cout, writes along Cin, both coalesced (an element-per-thread version with
-// stride-Cout reads took 103 us for the 49 layers of the UNet, 11 M weights).
+// stride-Cout reads took 103 us for the 49 layers of the UNet, 11 M weights).  The 16-bit passes take the same launch
+// with T = __bf16 / _Float16: every weight rounded to nearest even as it is stored (the values of wsis_weight_cast_lp).
 constexpr int WT_MAX = 64;
 constexpr int WT_TILE = 32;
 struct WtBatch {
   const float* src[WT_MAX];
-  float* dst[WT_MAX];
+  void* dst[WT_MAX];      // T [K, Cout, Cin]
   int K[WT_MAX], Cin[WT_MAX], Cout[WT_MAX], flip[WT_MAX];
   int start[WT_MAX + 1];   // first tile of each layer
   int n;
 };
 
+template <typename T>
 __global__ __launch_bounds__(256) void weight_transpose_batch_kernel(WtBatch b) {
   __shared__ float tile[WT_TILE][WT_TILE + 1];
   const int t = blockIdx.x;
@@ -112,7 +134,7 @@ __global__ __launch_bounds__(256) void weight_transpose_batch_kernel(WtBatch b) 
   const int kt = u / ti;               // slice of the OUTPUT [K, Cout, Cin]
   const int ks = b.flip[lo] ? (K - 1 - kt) : kt;
   const float* __restrict__ src = b.src[lo] + (int64_t)ks * Cin * Cout;
-  float* __restrict__ dst = b.dst[lo] + (int64_t)kt * Cin * Cout;
+  T* __restrict__ dst = static_cast<T*>(b.dst[lo]) + (int64_t)kt * Cin * Cout;
   const int x = threadIdx.x & 31, y0 = threadIdx.x >> 5;
 #pragma unroll
   for (int y = y0; y < WT_TILE; y += 8) {
@@ -123,7 +145,7 @@ __global__ __launch_bounds__(256) void weight_transpose_batch_kernel(WtBatch b) 
 #pragma unroll
   for (int y = y0; y < WT_TILE; y += 8) {
     const int co = bo * WT_TILE + y, ci = bi * WT_TILE + x;
-    if (ci < Cin && co < Cout) dst[(int64_t)co * Cin + ci] = tile[x][y];
+    if (ci < Cin && co < Cout) dst[(int64_t)co * Cin + ci] = (T)tile[x][y];
   }
 }
 
@@ -335,9 +357,47 @@ inline bool use_fwd2(const wsis_op& op, bool on) {
 }
 // does op need a transposed copy of its weights?  forward on the new kernel (B^T layout); dIn on the old one
 inline bool needs_wt(const wsis_op& op, bool on) {
+  if (op.flags & WSIS_OPF_LP) return false;      // (16-bit weights: lp_wt_bytes_of, cast at the top of the call)
   if (op.kind == WSIS_OP_CONV) return use_fwd2(op, on);
   if (op.kind == WSIS_OP_CONV_BWD) return op.out[0] != nullptr && !use_fwd2(op, on);
   return false;
+}
+
+// ---- 16-bit ops (WSIS_OPF_LP, evaluation-mode inference): what the executor runs, and why it refuses the rest
+inline bool is_lp(const wsis_op& op) { return (op.flags & WSIS_OPF_LP) != 0; }
+inline bool is_lp_conv(const wsis_op& op) { return op.kind == WSIS_OP_CONV && is_lp(op); }
+// 16-bit B^T weights [K, Cout, Cin] of a 16-bit convolution in the call's workspace
+inline int64_t lp_wt_bytes_of(const wsis_op& op) { return up((int64_t)op.K * op.Cin * op.Cout * 2); }
+// nullptr: op is not flagged or the executor runs it; otherwise why not
+const char* lp_refusal(const wsis_op& op) {
+  if (op.kind == WSIS_OP_CAST_LP && !is_lp(op)) return "CAST_LP without WSIS_OPF_LP (its dtype)";
+  if (!is_lp(op)) return nullptr;
+  if (op.reserved != 0 && op.reserved != 1) return "16-bit op with a dtype other than 0 (bf16) or 1 (fp16)";
+  switch (op.kind) {
+    case WSIS_OP_CONV:
+      if (op.flags & (WSIS_OPF_BN_IN | WSIS_OPF_STAT_FIN | WSIS_OPF_STATS))
+        return "16-bit convolution with a fused BatchNorm form or statistics (inference passes apply BatchNorm as an op)";
+      if (!wsis_spconv_lp_supported(op.K, op.Cin, op.Cout))
+        return "16-bit convolution outside wsis_spconv_lp_supported (channels multiples of 32, at most 512)";
+      if (op.M_in * op.Cin * 2 >= ((int64_t)1 << 31)) return "16-bit convolution input of 2 GiB or more";
+      if (!op.in[3]) return "16-bit convolution without weights";
+      return nullptr;
+    case WSIS_OP_BN_RELU:
+      if (op.flags & (WSIS_OPF_TRAINING | WSIS_OPF_UPDATE_RUNNING | WSIS_OPF_STATS))
+        return "16-bit BatchNorm in training form (the 16-bit pass is evaluation-mode only: running statistics)";
+      if (!op.in[3] || !op.in[4] || !op.out[0]) return "16-bit BatchNorm without running statistics or output";
+      return nullptr;
+    case WSIS_OP_CAT:
+      if ((op.Cin | op.Cout) & 1) return "16-bit concatenation of an odd channel count";
+      return nullptr;
+    case WSIS_OP_CAST_LP:
+      return nullptr;
+    case WSIS_OP_CONV_BWD:
+    case WSIS_OP_BN_RELU_BWD:
+      return "16-bit backward op (the 16-bit pass is inference only)";
+    default:
+      return "16-bit form of an op kind that has none";
+  }
 }
 
 // slab workspace of an op's weight-gradient product (the own-rows form when its input BatchNorm is applied on the fly)
@@ -347,8 +407,10 @@ inline int64_t dw_ws_of(const wsis_op& op) {
 }
 
 int64_t op_ws_bytes(const wsis_op& op, bool on) {
+  if (lp_refusal(op)) return -1;
   switch (op.kind) {
     case WSIS_OP_CONV:
+      if (is_lp(op)) return up(wsis_spconv_fwd_lp_workspace_bytes(op.M_out, op.K, op.Cin, op.Cout));
 #if WSIS_EXPERIMENTAL
       if (op.flags & (WSIS_OPF_BN_IN | WSIS_OPF_STAT_FIN))
         return up(std::max(wsis_spconv_fwd_f_workspace_bytes(op.M_out, op.K, op.Cin, op.Cout),
@@ -397,6 +459,7 @@ inline int paired_bn(const wsis_op* ops, int n, int i) {
 
 bool deep_op_ok(const wsis_op* ops, int n, int i, bool fwd2_on) {
   const wsis_op& op = ops[i];
+  if (is_lp(op)) return false;      // (the resident kernel's phases are fp32)
   const int64_t R = deep_max_rows();
   int nw = 0, zs = 0;
   switch (op.kind) {
@@ -697,6 +760,7 @@ int64_t wsis_run_ops_workspace_bytes(const wsis_op* ops, int32_t n) {
     if (dw_tail_on_main(ops, n, i)) b = std::max(b, dw_ws_of(ops[i]));      // (its slabs live in the op workspace)
     if (b > need) need = b;
     if (needs_wt(ops[i], on)) wt += wt_bytes_of(ops[i]);
+    if (is_lp_conv(ops[i])) wt += lp_wt_bytes_of(ops[i]);      // (the 16-bit weights, a region of their own)
     if (ops[i].kind == WSIS_OP_CONV_BWD && ops[i].out[1]) {
       const int64_t d = dw_ws_of(ops[i]);
       if (d < 0) return -1;
@@ -804,9 +868,59 @@ static int run_ops_impl(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_by
                         int32_t mark_op, void* waiter_stream, bool defer_join) {
   WSIS_REQUIRE((ops || n == 0) && n >= 0, "bad op list");
   WSIS_REQUIRE(mark_op < n && (mark_op < 0 || waiter_stream), "bad milestone");
+  for (int i = 0; i < n; ++i) {
+    const char* why = lp_refusal(ops[i]);
+    if (why) return fail(WSIS_ERR_ARG, "wsis_run_ops: op %d: %s", i, why);
+  }
   WSIS_REQUIRE((n == 0 || ws_bytes >= wsis_run_ops_workspace_bytes(ops, n)) && (d_ws || n == 0), "workspace too small");
   hipStream_t st = as_stream(stream);
   char* ws = static_cast<char*>(d_ws);
+  // ---- the 16-bit B^T weights of the pass's 16-bit convolutions, cast from the fp32 masters in THIS call (the pass
+  // follows every optimizer step), WT_MAX layers of one dtype per launch, on the caller's stream and before any fork
+  // below: an error here leaves nothing to join
+  std::vector<int64_t> lp_off(n, -1);
+  int64_t lp_total = 0;
+  {
+    WtBatch b;
+    b.n = 0;
+    b.start[0] = 0;
+    int dtype = 0;
+    auto flush = [&]() -> int {
+      if (b.n == 0) return WSIS_OK;
+      if (dtype == 0)
+        hipLaunchKernelGGL(weight_transpose_batch_kernel<__bf16>, dim3(b.start[b.n]), dim3(256), 0, st, b);
+      else
+        hipLaunchKernelGGL(weight_transpose_batch_kernel<_Float16>, dim3(b.start[b.n]), dim3(256), 0, st, b);
+      WSIS_LAUNCH_CHECK();
+      b.n = 0;
+      return WSIS_OK;
+    };
+    for (int i = 0; i < n; ++i) {
+      const wsis_op& op = ops[i];
+      if (!is_lp_conv(op)) continue;
+      if (b.n == WT_MAX || (b.n > 0 && op.reserved != dtype)) {
+        const int rc = flush();
+        if (rc != WSIS_OK) return rc;
+      }
+      dtype = op.reserved;
+      lp_off[i] = lp_total;
+      b.src[b.n] = (const float*)op.in[3];
+      b.dst[b.n] = ws + lp_total;
+      b.K[b.n] = op.K;
+      b.Cin[b.n] = op.Cin;
+      b.Cout[b.n] = op.Cout;
+      b.flip[b.n] = (op.flags & WSIS_OPF_FLIP) ? 1 : 0;
+      b.start[b.n + 1] = b.start[b.n] + op.K * ((op.Cin + WT_TILE - 1) / WT_TILE) * ((op.Cout + WT_TILE - 1) / WT_TILE);
+      ++b.n;
+      lp_total += lp_wt_bytes_of(op);
+    }
+    const int rc = flush();
+    if (rc != WSIS_OK) return rc;
+  }
+  char* const lp_base = ws;
+  ws += lp_total;
+  ws_bytes -= lp_total;
+  char* const wt_base = ws;
   // ---- all transposed weights of the pass, WT_MAX layers per launch; wt_off[i] = offset of op i's W^T
   const bool on = fwd2_enabled();
   std::vector<int64_t> wt_off(n, -1);
@@ -840,7 +954,7 @@ static int run_ops_impl(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_by
     b.start[0] = 0;
     auto flush = [&]() -> int {
       if (b.n == 0) return WSIS_OK;
-      hipLaunchKernelGGL(weight_transpose_batch_kernel, dim3(b.start[b.n]), dim3(256), 0, wt_st, b);
+      hipLaunchKernelGGL(weight_transpose_batch_kernel<float>, dim3(b.start[b.n]), dim3(256), 0, wt_st, b);
       WSIS_LAUNCH_CHECK();
       b.n = 0;
       return WSIS_OK;
@@ -876,7 +990,6 @@ static int run_ops_impl(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_by
   }
   ws += wt_total;
   ws_bytes -= wt_total;
-  char* const wt_base = static_cast<char*>(d_ws);
   // dW region (shared by the dW launches, which are ordered among themselves on one stream)
   // ... or, with deferred slab sums, one region per product: its slabs live until the batched launch that sums them
   const bool dw_defer = dw_batch_reduce_enabled();
@@ -1059,6 +1172,12 @@ static int run_ops_impl(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_by
     if (is_bn && g_prof_on) bn_prof.emplace(2, st);
     switch (op.kind) {
       case WSIS_OP_CONV:
+        if (is_lp(op)) {      // 16-bit: X, residual and Y in op.reserved's dtype, weights cast at the top of the call
+          rc = wsis_spconv_fwd_lp_res(op.in[0], (const int32_t*)op.in[1], (const int32_t*)op.in[2], lp_base + lp_off[i],
+                                      0, (const float*)op.in[4], op.in[5], op.out[0], op.M_in, op.M_out, op.K, op.Cin,
+                                      op.Cout, op.reserved, ws, ws_bytes, stream);
+          break;
+        }
         if (op.flags & (WSIS_OPF_BN_IN | WSIS_OPF_STAT_FIN)) {
 #if !WSIS_EXPERIMENTAL
           rc = fail(WSIS_ERR_ARG, "op %d: the fused BatchNorm forms of the convolution are in the EXPERIMENTAL build only", i);
@@ -1119,6 +1238,12 @@ static int run_ops_impl(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_by
                                (float*)op.out[0], op.M_in, op.M_out, op.K, op.Cin, op.Cout, ws, ws_bytes, stream);
         break;
       case WSIS_OP_BN_RELU: {
+        if (is_lp(op)) {      // evaluation form: the running statistics, 16-bit x, 16-bit (or fp32) y
+          rc = wsis_bn_apply_lp(op.in[0], (const float*)op.in[3], (const float*)op.in[4], (const float*)op.in[1],
+                                (const float*)op.in[2], op.eps, (op.flags & WSIS_OPF_RELU) ? 1 : 0, op.out[0],
+                                (op.flags & WSIS_OPF_OUT_F32) ? 1 : 0, op.M_in, op.Cin, op.reserved, stream);
+          break;
+        }
         const float* mean = (const float*)op.out[1];
         const float* var = (const float*)op.out[2];
         if (op.flags & WSIS_OPF_TRAINING) {
@@ -1159,17 +1284,39 @@ static int run_ops_impl(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_by
       }
       case WSIS_OP_CAT:
         if (op.M_in > 0) {
-          if (vec4_ok(op, op.in[0], op.in[1], op.out[0]))
-            hipLaunchKernelGGL(cat_rows_kernel<4>, dim3(grid_for(op.M_in * (op.Cin + op.Cout) / 4, 256)), dim3(256), 0,
-                               st, (const float*)op.in[0], (const float*)op.in[1], (float*)op.out[0], op.M_in, op.Cin,
-                               op.Cout);
+          // a 16-bit [M, C] tensor with C even is an [M, C / 2] tensor of 4-byte words: the fp32 concatenation with
+          // halved channel counts copies every 16-bit value bit for bit (no kernel of its own)
+          wsis_op c = op;
+          if (is_lp(op)) {
+            c.Cin /= 2;
+            c.Cout /= 2;
+          }
+          if (vec4_ok(c, c.in[0], c.in[1], c.out[0]))
+            hipLaunchKernelGGL(cat_rows_kernel<4>, dim3(grid_for(c.M_in * (c.Cin + c.Cout) / 4, 256)), dim3(256), 0,
+                               st, (const float*)c.in[0], (const float*)c.in[1], (float*)c.out[0], c.M_in, c.Cin,
+                               c.Cout);
           else
-            hipLaunchKernelGGL(cat_rows_kernel<1>, dim3(grid_for(op.M_in * (op.Cin + op.Cout), 256)), dim3(256), 0, st,
-                               (const float*)op.in[0], (const float*)op.in[1], (float*)op.out[0], op.M_in, op.Cin,
-                               op.Cout);
+            hipLaunchKernelGGL(cat_rows_kernel<1>, dim3(grid_for(c.M_in * (c.Cin + c.Cout), 256)), dim3(256), 0, st,
+                               (const float*)c.in[0], (const float*)c.in[1], (float*)c.out[0], c.M_in, c.Cin,
+                               c.Cout);
           RUN_LAUNCH_CHECK();
         }
         break;
+      case WSIS_OP_CAST_LP: {
+        const int64_t ne = op.M_in * op.Cin;
+        if (ne > 0) {
+          const bool vec = ne % 4 == 0 && ((reinterpret_cast<uintptr_t>(op.in[0]) & 15) | (reinterpret_cast<uintptr_t>(op.out[0]) & 7)) == 0;
+          const int64_t items = vec ? ne / 4 : ne;
+          if (op.reserved == 0)
+            hipLaunchKernelGGL(cast_lp_kernel<__bf16>, dim3(grid_for(items, 256)), dim3(256), 0, st,
+                               (const float*)op.in[0], (__bf16*)op.out[0], ne, vec ? 1 : 0);
+          else
+            hipLaunchKernelGGL(cast_lp_kernel<_Float16>, dim3(grid_for(items, 256)), dim3(256), 0, st,
+                               (const float*)op.in[0], (_Float16*)op.out[0], ne, vec ? 1 : 0);
+          RUN_LAUNCH_CHECK();
+        }
+        break;
+      }
       case WSIS_OP_SPLIT:
         if (op.M_in > 0) {
           if (vec4_ok(op, op.in[0], op.out[0], op.out[1]))

@@ -1,6 +1,7 @@
 // 16-bit sparse convolutions (bf16 / fp16 operands, fp32 accumulation) on the gfx950 matrix cores:
 //
-//   forward / dIn : out[r, :] = sum_k X[nbr[k][r], :] @ W[k]        X, WT 16-bit, out 16-bit (rounded once, at the end)
+//   forward / dIn : out[r, :] = sum_k X[nbr[k][r], :] @ W[k] (+ bias + residual)   X, WT, residual 16-bit, out 16-bit
+//                   (rounded once, at the end)
 //   weight grad   : dW[k]     = sum_r X[nbr[k][r], :]^T (x) dY[r, :]  X, dY 16-bit, dW fp32
 //
 // Forward / dIn: one wave owns 32 rows of the tile order x NT * 32 output channels.  With the 32x32x16 lane map lane l
@@ -64,7 +65,8 @@ __device__ __forceinline__ void chan_step(const T* xa, const T* wb, bool have, i
 template <typename T, int NT>
 __global__ __launch_bounds__(256) void spconv_lp_fwd_kernel(const T* __restrict__ X, const int32_t* __restrict__ nbr,
                                                             const int32_t* __restrict__ order, const T* __restrict__ WT,
-                                                            int flip, const float* __restrict__ bias, T* __restrict__ out,
+                                                            int flip, const float* __restrict__ bias,
+                                                            const T* __restrict__ res, T* __restrict__ out,
                                                             int64_t M_out, int K, int Cin, int Cout, int ncg) {
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
   const int cg = blockIdx.x % ncg;
@@ -90,7 +92,8 @@ __global__ __launch_bounds__(256) void spconv_lp_fwd_kernel(const T* __restrict_
     for (; c0 + 64 <= Cin; c0 += 64) chan_step<T, NT, 4>(xa, wb, src >= 0, c0, Cin, acc);
     if (c0 < Cin) chan_step<T, NT, 2>(xa, wb, src >= 0, c0, Cin, acc);
   }
-  // epilogue: register i of lane (r, h) is tile row (i & 3) + 8 (i >> 2) + 4h, column r
+  // epilogue: register i of lane (r, h) is tile row (i & 3) + 8 (i >> 2) + 4h, column r.  acc + bias (+ the residual,
+  // widened exactly) in fp32, then ONE rounding; without a residual nothing is added (bit-identical to the form without)
   const int64_t my_row = live ? (order ? (int64_t)order[t] : t) : -1;
 #pragma unroll
   for (int n = 0; n < NT; ++n) {
@@ -100,7 +103,11 @@ __global__ __launch_bounds__(256) void spconv_lp_fwd_kernel(const T* __restrict_
     for (int i = 0; i < 16; ++i) {
       const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
       const int64_t orow = __shfl(my_row, row);
-      if (orow >= 0) out[orow * Cout + col] = (T)(acc[n][i] + b);
+      if (orow >= 0) {
+        float v = acc[n][i] + b;
+        if (res) v += (float)res[orow * Cout + col];
+        out[orow * Cout + col] = (T)v;
+      }
     }
   }
 }
@@ -239,20 +246,20 @@ LpPlan lp_plan(int64_t M_out, int K, int Cin, int Cout) {
 
 template <typename T, int NT>
 void launch_fwd(const void* X, const int32_t* nbr, const int32_t* order, const void* WT, int flip, const float* bias,
-                void* out, int64_t M_out, int K, int Cin, int Cout, const LpPlan& p, hipStream_t st) {
+                const void* res, void* out, int64_t M_out, int K, int Cin, int Cout, const LpPlan& p, hipStream_t st) {
   hipLaunchKernelGGL((spconv_lp_fwd_kernel<T, NT>), dim3((unsigned)p.fwd_blocks), dim3(64 * LP_WAVES), 0, st,
-                     static_cast<const T*>(X), nbr, order, static_cast<const T*>(WT), flip, bias, static_cast<T*>(out),
-                     M_out, K, Cin, Cout, p.ncg);
+                     static_cast<const T*>(X), nbr, order, static_cast<const T*>(WT), flip, bias,
+                     static_cast<const T*>(res), static_cast<T*>(out), M_out, K, Cin, Cout, p.ncg);
 }
 
 template <typename T>
 void launch_fwd_t(const void* X, const int32_t* nbr, const int32_t* order, const void* WT, int flip, const float* bias,
-                  void* out, int64_t M_out, int K, int Cin, int Cout, hipStream_t st) {
+                  const void* res, void* out, int64_t M_out, int K, int Cin, int Cout, hipStream_t st) {
   const LpPlan p = lp_plan(M_out, K, Cin, Cout);
   if (p.nt == 2)
-    launch_fwd<T, 2>(X, nbr, order, WT, flip, bias, out, M_out, K, Cin, Cout, p, st);
+    launch_fwd<T, 2>(X, nbr, order, WT, flip, bias, res, out, M_out, K, Cin, Cout, p, st);
   else
-    launch_fwd<T, 1>(X, nbr, order, WT, flip, bias, out, M_out, K, Cin, Cout, p, st);
+    launch_fwd<T, 1>(X, nbr, order, WT, flip, bias, res, out, M_out, K, Cin, Cout, p, st);
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -284,6 +291,14 @@ int64_t wsis_spconv_fwd_lp_workspace_bytes(int64_t M_out, int32_t K, int32_t Cin
 int wsis_spconv_fwd_lp(const void* d_X, const int32_t* d_nbr, const int32_t* d_order, const void* d_WT, int32_t flip,
                        const float* d_bias, void* d_out, int64_t M_in, int64_t M_out, int32_t K, int32_t Cin,
                        int32_t Cout, int32_t dtype, void* d_ws, int64_t ws_bytes, void* stream) {
+  return wsis_spconv_fwd_lp_res(d_X, d_nbr, d_order, d_WT, flip, d_bias, nullptr, d_out, M_in, M_out, K, Cin, Cout, dtype,
+                                d_ws, ws_bytes, stream);
+}
+
+int wsis_spconv_fwd_lp_res(const void* d_X, const int32_t* d_nbr, const int32_t* d_order, const void* d_WT,
+                           int32_t flip, const float* d_bias, const void* d_residual, void* d_out, int64_t M_in,
+                           int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* d_ws,
+                           int64_t ws_bytes, void* stream) {
   (void)d_ws;
   (void)ws_bytes;
   WSIS_REQUIRE(M_in >= 0 && M_out >= 0, "bad sizes");
@@ -297,9 +312,9 @@ int wsis_spconv_fwd_lp(const void* d_X, const int32_t* d_nbr, const int32_t* d_o
   WSIS_REQUIRE(aligned16(d_X) && aligned16(d_WT), "X and WT must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
   if (dtype == 0)
-    launch_fwd_t<__bf16>(d_X, d_nbr, d_order, d_WT, flip, d_bias, d_out, M_out, K, Cin, Cout, st);
+    launch_fwd_t<__bf16>(d_X, d_nbr, d_order, d_WT, flip, d_bias, d_residual, d_out, M_out, K, Cin, Cout, st);
   else
-    launch_fwd_t<_Float16>(d_X, d_nbr, d_order, d_WT, flip, d_bias, d_out, M_out, K, Cin, Cout, st);
+    launch_fwd_t<_Float16>(d_X, d_nbr, d_order, d_WT, flip, d_bias, d_residual, d_out, M_out, K, Cin, Cout, st);
   WSIS_LAUNCH_CHECK();
   return WSIS_OK;
 }

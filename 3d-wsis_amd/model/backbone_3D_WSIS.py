@@ -132,7 +132,24 @@ class Network(nn.Module):
         fp32_pass = input.features.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
         self.last_pass = "native" if (input.features.is_cuda and fp32_pass and os.environ.get("WSIS_NATIVE_UNET", "1") != "0"
                                       and (not sync_bn or sync_native)) else "modules"
-        if self.last_pass == "native":
+        # ... except an evaluation-mode forward without gradients in 16 bits with WSIS_NATIVE_LP=1: the 16-bit native
+        # pass (unet_native.lp_pass_wanted)
+        lp_dtype = spconv.ops.compute_dtype(input.features) if input.features.is_cuda else None
+        if self.last_pass == "modules" and lp_dtype is not None and os.environ.get("WSIS_NATIVE_LP", "0") == "1":
+            import unet_native
+            # (the model's conditions as callables: they run only in a no-gradient pass in 16 bits)
+            if unet_native.lp_pass_wanted(os.environ, lp_dtype, torch.is_grad_enabled(),
+                                          lambda: unet_native.lp_params_fp32(self, input.features.device),
+                                          lambda: unet_native.lp_bn_eval(self),
+                                          lambda: unet_native.lp_in_domain(self, int(input.features.shape[0]))):
+                self.last_pass = "native_lp"
+        if self.last_pass == "native_lp":
+            voxel_feats = unet_native.run_unet_lp(self, input, lp_dtype,
+                                                  unet_native.lp_out_dtype(lp_dtype, torch.is_autocast_enabled("cuda")))
+            if branch is not None:
+                for gconv in self.ecc.gconvs:
+                    gconv.prefetch_filter_state(branch, params_ready)
+        elif self.last_pass == "native":
             # input_conv -> unet -> output_layer recorded as an op list and issued by one native call per pass
             # (model/unet_native.py); WSIS_NATIVE_UNET=0 walks the modules instead (same kernels, same results)
             import unet_native

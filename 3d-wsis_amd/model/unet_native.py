@@ -14,8 +14,10 @@ Activations live in one arena per pass (bump allocation, nothing is freed before
 rematerialisation pointless at these sizes), parameter gradients densely in one flat buffer whose views become
 ``p.grad`` (and which ``parallel.GradSync`` all-reduces in place).
 
-The op list is fp32 only: ``Network.forward`` takes this pass for fp32 features outside autocast, and walks the modules
-(16-bit sparse convolutions, spconv.ops.compute_dtype) for 16-bit features or under ``torch.autocast``.
+The training op list is fp32 only: ``Network.forward`` takes this pass for fp32 features outside autocast.  For 16-bit
+features or under ``torch.autocast`` (spconv.ops.compute_dtype) it walks the modules -- except for an evaluation-mode
+forward without gradients with WSIS_NATIVE_LP=1 (``lp_pass_wanted``), which runs the 16-bit forward program of
+``UNetProgram.compiled_lp`` (``run_unet_lp``).
 """
 import os
 
@@ -31,6 +33,8 @@ from spconv import ops as sp_ops
 OP_CONV, OP_BN_RELU, OP_CAT, OP_SPLIT, OP_ADD, OP_CONV_BWD, OP_BN_RELU_BWD = 1, 2, 3, 4, 5, 6, 7
 F_RELU, F_TRAINING, F_UPDATE, F_FLIP, F_STATS, F_BN_IN, F_STAT_FIN = 1, 2, 4, 8, 16, 32, 64
 N_IN, N_OUT = 12, 8
+OP_CAST_LP = 8
+F_LP, F_OUT_F32 = 128, 256      # 16-bit op (dtype code in wsis_op.reserved); fp32 output of a 16-bit BatchNorm op
 
 OP_DTYPE = np.dtype([("kind", "<i4"), ("flags", "<i4"), ("M_in", "<i8"), ("M_out", "<i8"), ("K", "<i4"),
                      ("Cin", "<i4"), ("Cout", "<i4"), ("reserved", "<i4"), ("eps", "<f4"), ("momentum", "<f4"),
@@ -425,6 +429,98 @@ class UNetProgram(object):
                 d_x = b(recb, d_x)
             return d_x
         return x, bwd
+
+    # ---- the 16-bit evaluation-mode forward (F_LP ops): a 16-bit activation of C channels is C / 2 floats per row of the
+    # arena.  Running statistics only, BatchNorm applied by ops of its own (no statistics, no fused forms), no backward.
+    def _lp_conv(self, rec, x, conv, table, lvl_in, lvl_out, residual=0):
+        K = int(np.prod(conv.kernel_size))
+        Cin, Cout = conv.in_channels, conv.out_channels
+        assert conv.bias is None, "the UNet convolutions carry no bias (sparse_unet3d.py)"
+        t = table if table is not None else _Table()
+        y = rec.alloc(lvl_out, Cout // 2)
+        # (the executor casts the fp32 weight to 16-bit B^T slices inside the call: the pass follows the optimizer)
+        rec.op(OP_CONV, F_LP, _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
+               inp=(x, t.nbr_f, t.order_f, conv.weight.data_ptr(), 0, residual), out=(y,))
+        return y
+
+    def _lp_bn_relu(self, rec, x, bn, lvl, relu=True, out_f32=False):
+        C = bn.num_features
+        y = rec.alloc(lvl, C if out_f32 else C // 2)
+        flags = F_LP | (F_RELU if relu else 0) | (F_OUT_F32 if out_f32 else 0)
+        rec.op(OP_BN_RELU, flags, _lvl(lvl), _lvl(lvl), 0, C, C, bn.eps, 0.0,
+               inp=(x, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var)), out=(y,))
+        return y
+
+    def _lp_residual_block(self, rec, x, blk, lvl):
+        seq = blk.conv_branch
+        bn1, conv1, bn2, conv2 = seq[0], seq[2], seq[3], seq[5]
+        table = _subm(lvl)
+        a1 = self._lp_bn_relu(rec, x, bn1, lvl)
+        z1 = self._lp_conv(rec, a1, conv1, table, lvl, lvl)
+        a2 = self._lp_bn_relu(rec, z1, bn2, lvl)
+        first = blk.i_branch[0]
+        res = x if isinstance(first, nn.Identity) else self._lp_conv(rec, x, first, None, lvl, lvl)
+        # the skip path is added in conv2's epilogue before its one rounding (the walk adds two rounded tensors)
+        return self._lp_conv(rec, a2, conv2, table, lvl, lvl, residual=res)
+
+    def _lp_ublock(self, rec, x, ub, lvl):
+        for blk in ub.blocks:
+            x = self._lp_residual_block(rec, x, blk, lvl)
+        if len(ub.nPlanes) == 1:
+            return x
+        C0 = ub.nPlanes[0]
+        a = self._lp_bn_relu(rec, x, ub.conv[0], lvl)
+        d = self._lp_conv(rec, a, ub.conv[2], _down(lvl), lvl, lvl + 1)
+        u = self._lp_ublock(rec, d, ub.u, lvl + 1)
+        a2 = self._lp_bn_relu(rec, u, ub.deconv[0], lvl + 1)
+        up = self._lp_conv(rec, a2, ub.deconv[2], _up(lvl), lvl + 1, lvl)
+        cat = rec.alloc(lvl, C0)                  # 2 * C0 16-bit channels
+        rec.op(OP_CAT, F_LP, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(x, up), out=(cat,))
+        x = cat
+        for blk in ub.blocks_tail:
+            x = self._lp_residual_block(rec, x, blk, lvl)
+        return x
+
+    def compiled_lp(self, dtype, out_f32):
+        """the 16-bit evaluation-mode forward program of ``dtype`` (bf16 / fp16); ``out_f32``: the output layer's
+        BatchNorm+ReLU stores fp32.  The output is external slot 1 (a tensor of the caller's): the arena of the pass is
+        free once the call has been issued."""
+        # (dtypes in the key too: a parameter converted to 16 bits may reuse a freed fp32 address)
+        key = ("lp", dtype, bool(out_f32), tuple((p.data_ptr(), p.dtype) for p in self.params),
+               tuple((_ptr(bn.running_mean), _ptr(bn.running_var), bn.running_var.dtype if bn.running_var is not None
+                      else None) for bn in self.bns))
+        c = self._cache.get(key)
+        if c is not None:
+            return c
+        if len(self._cache) > 8:
+            self._cache.clear()
+        net = self.net
+        dev = net.input_conv[0].weight.device
+        if not lp_params_fp32(net, dev):
+            raise ValueError("the 16-bit native pass reads the model's parameters and running statistics as contiguous "
+                             "fp32 tensors (lp_params_fp32); a model with 16-bit parameters walks the modules")
+        rec = _Recorder(_FWD)
+        # the 6 -> 32 input convolution lies outside the 16-bit domain: the fp32 op, its output rounded once (what the
+        # module walk's fallback does, spconv.ops._forward_lp)
+        conv0 = net.input_conv[0]
+        K0, C0 = int(np.prod(conv0.kernel_size)), conv0.out_channels
+        t0 = _subm(0)
+        y32 = rec.alloc(0, C0)
+        rec.op(OP_CONV, 0, _lvl(0), _lvl(0), K0, conv0.in_channels, C0,
+               inp=(_EXT | 0, t0.nbr_f, t0.order_f, conv0.weight.data_ptr(), 0, 0), out=(y32,))
+        y = rec.alloc(0, C0 // 2)
+        rec.op(OP_CAST_LP, F_LP, _lvl(0), _lvl(0), 0, C0, C0, inp=(y32,), out=(y,))
+        y = self._lp_ublock(rec, y, net.unet, 0)
+        bn = net.output_layer[0]
+        C = bn.num_features
+        rec.op(OP_BN_RELU, F_LP | F_RELU | (F_OUT_F32 if out_f32 else 0), _lvl(0), _lvl(0), 0, C, C, bn.eps, 0.0,
+               inp=(y, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var)), out=(_EXT | 1,))
+        c = _Compiled()
+        c.fwd, c.fwd_arena = _Template(rec), _Arena(rec)
+        c.fwd.arr["reserved"] = np.where((c.fwd.arr["flags"] & F_LP) != 0, sp_ops._LP_DTYPES[dtype], 0)
+        c.out_channels = C
+        self._cache[key] = c
+        return c
 
     def _grad_handle(self, p):
         # parameter gradients live densely in their own flat buffer (one all-reduce for data parallelism)
@@ -867,6 +963,90 @@ def _check_experimental_switches():
         warnings.warn("tuning knob(s) %s are set but the DEFAULT libwsis_hip.so is loaded: they are live in the "
                       "EXPERIMENTAL build only (make -C 3d-wsis_amd/csrc EXPERIMENTAL=1) and have no effect here"
                       % ", ".join(ignored), RuntimeWarning, stacklevel=2)
+
+
+def lp_pass_wanted(env, compute_dtype, grad_enabled, params_fp32, bn_eval, in_domain):
+    """does ``Network.forward`` take the 16-bit native pass?  ``env``: the environment (WSIS_NATIVE_LP=1 switches it on,
+    WSIS_NATIVE_UNET=0 off), ``compute_dtype``: spconv.ops.compute_dtype of the input features, ``grad_enabled``:
+    torch.is_grad_enabled(); the model's conditions, each a bool or a callable that returns one: ``params_fp32``: every
+    parameter and running statistic the pass reads is a contiguous fp32 tensor on the features' device
+    (``lp_params_fp32``: the executor reads them as fp32 through raw pointers), ``bn_eval``: every BatchNorm layer of the
+    UNet in evaluation mode with running statistics (``lp_bn_eval``), ``in_domain``: every product inside
+    spconv.ops.lp_supported (``lp_in_domain``).  The cheap conditions come first: a callable runs only when everything
+    in front of it holds.  Pure: no device."""
+    if not (env.get("WSIS_NATIVE_LP", "0") == "1" and env.get("WSIS_NATIVE_UNET", "1") != "0"
+            and compute_dtype in (torch.bfloat16, torch.float16) and not grad_enabled):
+        return False
+    return all(bool(c() if callable(c) else c) for c in (params_fp32, bn_eval, in_domain))
+
+
+def _lp_modules(net):
+    return [m for mod in (net.unet, net.output_layer) for m in mod.modules()]
+
+
+def lp_params_fp32(net, device):
+    """every parameter of input_conv + unet + output_layer and every BatchNorm running statistic is a contiguous fp32
+    tensor on ``device`` (a model converted with ``.to(torch.bfloat16)`` walks the modules, which widen its weights)"""
+    dev = torch.device(device)
+    ts = [p for m in (net.input_conv, net.unet, net.output_layer) for p in m.parameters()]
+    ts += [t for m in _lp_modules(net) if isinstance(m, nn.BatchNorm1d) for t in (m.running_mean, m.running_var)
+           if t is not None]
+    return all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in ts)
+
+
+def lp_bn_eval(net):
+    """every BatchNorm layer of unet + output_layer normalises with its running statistics"""
+    return all(not m.training and m.track_running_stats and m.running_mean is not None and m.running_var is not None
+               for m in _lp_modules(net) if isinstance(m, nn.BatchNorm1d))
+
+
+def lp_in_domain(net, rows):
+    """every sparse product of the UNet (forward) inside spconv.ops.lp_supported; ``rows``: the finest level's row count,
+    an upper bound of every level's"""
+    import spconv
+    return all(sp_ops.lp_supported(int(np.prod(m.kernel_size)), m.in_channels, m.out_channels, rows)
+               for m in net.unet.modules() if isinstance(m, spconv.conv.SparseConvolution))
+
+
+def lp_out_dtype(compute_dtype, autocast):
+    """the dtype the module walk returns for the UNet: the output layer's BatchNorm1d keeps its 16-bit input's dtype
+    unless autocast casts batch_norm, then fp32.  torch's documented CUDA autocast lists do not name batch_norm; the
+    dispatcher is asked where it can be (a torch without that query: the documented behaviour)"""
+    has_kernel = getattr(torch._C, "_dispatch_has_kernel_for_dispatch_key", None)
+    if autocast and has_kernel is not None:
+        try:
+            if has_kernel("aten::batch_norm", "AutocastCUDA"):
+                return torch.float32
+        except (RuntimeError, TypeError):
+            pass
+    return compute_dtype
+
+
+def run_unet_lp(net, input_tensor, dtype, out_dtype):
+    """the 16-bit evaluation-mode forward of input_conv + unet + output_layer (no gradient): features -> [M0, m] of
+    ``out_dtype`` (``dtype`` or fp32).  The input features are rounded to ``dtype`` and widened, exactly what the walk's
+    input convolution reads; every 16-bit value of the pass is rounded once (input convolution output, convolution
+    epilogues after the residual, BatchNorm applies), concatenations copy bits."""
+    _check_experimental_switches()
+    prog = getattr(net, "_native_prog", None)
+    if prog is None:
+        prog = UNetProgram(net)
+        net._native_prog = prog
+    prog.bind(input_tensor)
+    x = input_tensor.features
+    _n.require_cuda(x)
+    x = x.detach().to(dtype).float().contiguous()
+    c = prog.compiled_lp(dtype, out_dtype == torch.float32)
+    Mvec = prog.Mvec
+    offs, total = c.fwd_arena.layout(Mvec)
+    arena, base = _arena_tensor(total, x.device)
+    out = torch.empty((int(Mvec[0]), c.out_channels), dtype=out_dtype, device=x.device)
+    none = np.zeros(0, dtype=np.uint64)
+    luts = {_FWD: offs.astype(np.uint64) + np.uint64(base), _TBL: prog.table_lut,
+            _EXT: np.array([x.data_ptr(), out.data_ptr()], dtype=np.uint64), _BWD: none, _PAR: none}
+    _run(_n.hip(), c.fwd.instantiate(Mvec, luts), x.device)
+    sp_ops.verify_pending_counts()
+    return out
 
 
 def run_unet(net, input_tensor, sync_group=None):

@@ -313,6 +313,13 @@ int64_t wsis_spconv_fwd_lp_workspace_bytes(int64_t M_out, int32_t K, int32_t Cin
 int wsis_spconv_fwd_lp(const void* d_X, const int32_t* d_nbr, const int32_t* d_order, const void* d_WT, int32_t flip,
                        const float* d_bias, void* d_out, int64_t M_in, int64_t M_out, int32_t K, int32_t Cin,
                        int32_t Cout, int32_t dtype, void* d_ws, int64_t ws_bytes, void* stream);
+/* The same with an optional 16-bit residual [M_out, Cout] (d_residual; NULL: exactly wsis_spconv_fwd_lp): each output
+ * element is acc + bias + residual in fp32, rounded to 16 bits ONCE -- the skip connection of the residual block
+ * (sparse_unet3d.py:163-172, the in[5] residual of the executor's fp32 CONV op).  d_residual must not alias d_out. */
+int wsis_spconv_fwd_lp_res(const void* d_X, const int32_t* d_nbr, const int32_t* d_order, const void* d_WT,
+                           int32_t flip, const float* d_bias, const void* d_residual, void* d_out, int64_t M_in,
+                           int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, int32_t dtype, void* d_ws,
+                           int64_t ws_bytes, void* stream);
 /* dW[k] = sum_r X[nbr[k][r]]^T (x) dY[r] with 16-bit X [M_in, Cin] and dY [M_out, Cout] -> fp32 d_dW [K, Cin, Cout]
  * (overwritten): the 16-bit form of wsis_spconv_dw [UPSTREAM spconv indiceConvBackward, filter gradient].  Partial slabs
  * per row chunk in d_ws, added in chunk order: no atomics, bit-reproducible. */
@@ -401,6 +408,13 @@ int wsis_bn_bwd_from_partials(const float* d_partials, int64_t n_part, const flo
 /* y = relu?( (x-mean)*rsqrt(var+eps)*gamma + beta )   (gamma/beta may be NULL = 1/0) */
 int wsis_bn_apply(const float* d_x, const float* d_mean, const float* d_var, const float* d_gamma,
                   const float* d_beta, float eps, int32_t relu, float* d_y, int64_t M, int32_t C, void* stream);
+/* The evaluation-mode apply for 16-bit x [M, C] (dtype 0 = bf16, 1 = fp16) with fp32 statistics and affine parameters:
+ * exactly the fp32 arithmetic of wsis_bn_apply on the widened x, rounded ONCE to 16 bits into d_y, or stored as fp32
+ * when out_fp32 (then d_y equals wsis_bn_apply of the widened x bit for bit).  C % 4 == 0: x and y aligned to four
+ * elements. */
+int wsis_bn_apply_lp(const void* d_x, const float* d_mean, const float* d_var, const float* d_gamma,
+                     const float* d_beta, float eps, int32_t relu, void* d_y, int32_t out_fp32, int64_t M, int32_t C,
+                     int32_t dtype, void* stream);
 /* backward of the fused BN(+ReLU): dgamma = sum dz*xhat, dbeta = sum dz (dz = dy masked by the ReLU),
  * dx = gamma*rstd*(dz - dbeta/M - xhat*dgamma/M) when training, gamma*rstd*dz otherwise; d_dx may be NULL.
  * d_addend (optional, [M,C]) is added to dx in the same pass: the gradient arriving over the residual skip
@@ -720,6 +734,7 @@ int wsis_adamw_step(const void* d_segments, const int32_t* d_blocks, int64_t n_b
  *   CONV_BWD     in: X, W, dY, nbr_f, order_f, nbr_b, order_b  out: dX (may be NULL), dW (may be NULL)
  *                M_in = rows of X / dX, M_out = rows of dY     (weight_transpose + wsis_spconv_fwd + wsis_spconv_dw)
  *   BN_RELU_BWD  in: x, dy, mean, var, gamma, beta, addend     out: dx, dgamma, dbeta      (wsis_bn_bwd)
+ *   CAST_LP      in: x fp32 [M_in, Cin]                        out: y 16-bit [M_in, Cin]   (round to nearest even)
  * BN ops use M_in rows and Cin channels.  d_ws from wsis_run_ops_workspace_bytes (max over the ops); d_sync: a
  * zero-filled block of wsis_sync_bytes() bytes (may be NULL: multi-launch forms).
  * Streams: everything the caller's later work depends on is ordered on `stream` when the call returns.  Work that the
@@ -730,7 +745,7 @@ int wsis_adamw_step(const void* d_segments, const int32_t* d_blocks, int64_t n_b
  * first op that reads one).  Same kernels on either stream: the results do not depend on these switches. */
 enum {
   WSIS_OP_CONV = 1, WSIS_OP_BN_RELU = 2, WSIS_OP_CAT = 3, WSIS_OP_SPLIT = 4, WSIS_OP_ADD = 5, WSIS_OP_CONV_BWD = 6,
-  WSIS_OP_BN_RELU_BWD = 7
+  WSIS_OP_BN_RELU_BWD = 7, WSIS_OP_CAST_LP = 8
 };
 /* WSIS_OPF_STATS on CONV: out[1] = BatchNorm partials of the output (wsis_spconv_fwd_t d_stats).
  * WSIS_OPF_STATS on BN_RELU (training): the statistics come from partials instead of a pass over x: in[5] = partials
@@ -743,9 +758,20 @@ enum {
  * WSIS_OPF_STAT_FIN on CONV (with WSIS_OPF_STATS): the statistics of the output are finished inside the launch for
  * n = 1 or 2 BatchNorm layers: target 0 = out[2] mean, out[3] var, in[10] running_mean, in[11] running_var, op.momentum;
  * target 1 (when out[4] != NULL) = out[4], out[5], out[6], out[7], op.momentum2. */
+/* WSIS_OPF_LP: a 16-bit op of an evaluation-mode inference pass; op.reserved = dtype (0 = bf16, 1 = fp16).
+ *   CONV     wsis_spconv_fwd_lp_res: X, residual (in[5]) and Y in 16 bits.  The 16-bit B^T weights are cast from the fp32
+ *            in[3] inside the same call (wsis_weight_cast_lp, transpose = 1; slice K-1-k with WSIS_OPF_FLIP) into the
+ *            call's workspace, so the pass follows every optimizer step.  Shape inside wsis_spconv_lp_supported.
+ *   BN_RELU  evaluation form only (running statistics in[3], in[4]): wsis_bn_apply_lp, 16-bit x; y in 16 bits, or fp32
+ *            with WSIS_OPF_OUT_F32.
+ *   CAT      the 16-bit concatenation is the fp32 CAT op with Cin / 2 and Cout / 2 (both even): it copies 4-byte words.
+ *   CAST_LP  carries the flag too (its dtype).
+ * A flagged op the executor cannot run (training BatchNorm, CONV_BWD, BN_RELU_BWD, a shape outside the 16-bit domain, a
+ * fused BatchNorm form) fails the call with WSIS_ERR_ARG before anything is launched.  Lists without the flag run as
+ * before. */
 enum {
   WSIS_OPF_RELU = 1, WSIS_OPF_TRAINING = 2, WSIS_OPF_UPDATE_RUNNING = 4, WSIS_OPF_FLIP = 8, WSIS_OPF_STATS = 16,
-  WSIS_OPF_BN_IN = 32, WSIS_OPF_STAT_FIN = 64
+  WSIS_OPF_BN_IN = 32, WSIS_OPF_STAT_FIN = 64, WSIS_OPF_LP = 128, WSIS_OPF_OUT_F32 = 256
 };
 typedef struct wsis_op {
   int32_t kind, flags;
