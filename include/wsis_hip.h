@@ -658,6 +658,23 @@ int wsis_bfs_order(const int32_t* d_idx, const int32_t* d_start_len, const int32
                    const int32_t* d_offsets, int64_t n_clusters, int32_t* d_pos, int32_t* d_stamp,
                    int32_t* d_cluster_idxs, void* stream);
 
+/* ---- S3DIS wall split: utils/planeSegment.py:29-63 (get_room_walls, called at test_s3dis.py:533), which runs open3d's
+ * PointCloud.segment_plane(distance, 3, iter) once per wall [UPSTREAM open3d].  One such call is `iter` candidate planes
+ * scored against every remaining wall point; wsis_plane_score scores all H candidates in one pass over the points.
+ * d_xyz fp32 [N,3]; d_planes fp64 [H,4] = (a, b, c, d), unit normal; dist_i = |((a*x + b*y) + c*z) + d| with x, y, z
+ * widened to fp64, in that order, uncontracted.  d_count[h] int64 = #{i : dist_i < thr} (strict; a non-finite
+ * coordinate is never an inlier), d_sumsq[h] fp64 = sum of dist_i^2 over those i.  The counts are exact; the sums are
+ * added in an order fixed by (N, H) (per-workgroup rows in d_ws, added in row order by a second launch: no atomics), so
+ * they are bit-reproducible.  1 <= H <= 1024 (more hypotheses: several calls); N == 0 writes zeros without a launch.
+ * The workspace query returns -1 for N < 0 or H outside [1, 1024]. */
+int64_t wsis_plane_score_workspace_bytes(int64_t N, int32_t H);
+int wsis_plane_score(const float* d_xyz, int64_t N, const double* d_planes, int32_t H, double thr, int64_t* d_count,
+                     double* d_sumsq, void* d_ws, int64_t ws_bytes, void* stream);
+/* utils/planeSegment.py:45-58 / open3d segment_plane's inlier index: d_mask uint8 [N], 1 where dist_i < thr for the ONE
+ * plane d_plane4 fp64 [4] -- the same expression and the same strict comparison as wsis_plane_score, so the number of
+ * ones equals that call's count. */
+int wsis_plane_mark(const float* d_xyz, int64_t N, const double* d_plane4, double thr, uint8_t* d_mask, void* stream);
+
 /* ---- a18 (point-level part): semantic loss of MultiTaskLoss.forward (losses_3D_WSIS.py:52-67 of the reference):
  * CrossEntropyLoss(ignore_index) + mean_c(1 - dice_c) with dice_c = (2 sum p_c y_c + 1e-5) / (sum p_c^2 + sum y_c
  * + 1e-4 + 1e-5) over the rows whose label != ignore_label, p = softmax(scores).  d_scores fp32 [N,C] (C <= 32),
