@@ -10,6 +10,10 @@ Numerically this is the same kernel sequence the per-module path (spconv.SubMCon
 so both paths agree bit for bit; what disappears is ~450 Python-dispatched autograd nodes per step
 (sparse_unet3d.py:103-350 walked by torch in the reference).
 
+The walk (``_residual_block`` / ``_ublock``) exists once and emits through ``_TrainEmitter`` (fp32 ops, backward closures,
+everything that lives for one recording) or ``_LpEmitter`` (16-bit forward); ops under construction are ``_Op`` records,
+their pointer slots go by the ``S_*`` names.  tests/test_unet_program_host.py pins the recordings byte for byte on the CPU.
+
 Activations live in one arena per pass (bump allocation, nothing is freed before the backward: 288 GB of HBM make
 rematerialisation pointless at these sizes), parameter gradients densely in one flat buffer whose views become
 ``p.grad`` (and which ``parallel.GradSync`` all-reduces in place).
@@ -19,7 +23,9 @@ features or under ``torch.autocast`` (spconv.ops.compute_dtype) it walks the mod
 forward without gradients with WSIS_NATIVE_LP=1 (``lp_pass_wanted``), which runs the 16-bit forward program of
 ``UNetProgram.compiled_lp`` (``run_unet_lp``).
 """
+import collections
 import os
+import types
 
 import numpy as np
 import torch
@@ -98,12 +104,55 @@ def _lvl(level):
     return -(level + 1)
 
 
+# slots of wsis_op.in[] / .out[] per op kind: the table in the comment above ``wsis_op`` in include/wsis_hip.h, by name
+class S_CONV(object):      # OP_CONV
+    X, NBR, ORDER, W, BIAS, RESIDUAL = range(6)                      # in[]
+    BN_IN = slice(6, 10)                                             # in[]: mean, var, gamma, beta (F_BN_IN)
+    FIN0_RUNNING = slice(10, 12)                                     # in[]: running mean, var of finish target 0
+    Y, PARTS = 0, 1                                                  # out[]: output, its BatchNorm partials (F_STATS)
+    FIN0 = slice(2, 4)                                               # out[]: mean, var of finish target 0 (F_STAT_FIN)
+    FIN1 = slice(4, 8)                                               # out[]: mean, var, running mean, running var of
+    FIN1_MEAN = 4                                                    # finish target 1 (momentum2); NULL mean: unused
+
+
+class S_CONV_BWD(object):      # OP_CONV_BWD
+    X, W, DY, NBR_F, ORDER_F, NBR_B, ORDER_B = range(7)              # in[]
+    BN_IN = slice(7, 11)                                             # in[]: mean, var, gamma, beta (F_BN_IN)
+    DX, DW = 0, 1                                                    # out[]
+
+
+class S_BN(object):      # OP_BN_RELU
+    X, GAMMA, BETA, RMEAN, RVAR = range(5)                           # in[]
+    PARTS0, PARTS1 = 5, 6                                            # in[]: partials of channels [0, K) and [K, Cin)
+    Y, MEAN, VAR = range(3)                                          # out[]
+
+
+class S_BN_BWD(object):      # OP_BN_RELU_BWD
+    X, DY, MEAN, VAR, GAMMA, BETA, ADDEND = range(7)                 # in[]
+    DIN_PARTS = 7                                                    # in[]: (sum dz, sum dz*xhat) partials of the dIn pass
+    DX, DGAMMA, DBETA = range(3)                                     # out[]
+
+
+class _Op(object):
+    """a ``wsis_op`` being recorded: one attribute per field of the struct, ``inp`` / ``out`` as lists of N_IN / N_OUT
+    handles (later ops patch earlier ones: statistics targets, epilogue reductions)"""
+    __slots__ = ("kind", "flags", "M_in", "M_out", "K", "Cin", "Cout", "eps", "momentum", "momentum2", "inp", "out")
+
+    def __init__(self, kind, flags=0, M_in=0, M_out=0, K=0, Cin=0, Cout=0, eps=0.0, momentum=0.0, inp=(), out=()):
+        """``inp`` / ``out``: the leading slots in the order of the S_* classes"""
+        self.kind, self.flags, self.M_in, self.M_out = kind, flags, M_in, M_out
+        self.K, self.Cin, self.Cout = K, Cin, Cout
+        self.eps, self.momentum, self.momentum2 = eps, momentum, 0.0
+        self.inp = list(inp) + [0] * (N_IN - len(inp))
+        self.out = list(out) + [0] * (N_OUT - len(out))
+
+
 class _Recorder(object):
     """symbolic op list + allocation table of one arena"""
 
     def __init__(self, tag, align=256):
         self.tag, self.align = tag, align
-        self.rows = []
+        self.ops = []
         self.alloc_level, self.alloc_mult, self.alloc_slices = [], [], []
 
     def alloc(self, level, mult, per_slice=False):
@@ -114,13 +163,10 @@ class _Recorder(object):
         self.alloc_slices.append(bool(per_slice))
         return self.tag | (len(self.alloc_level) - 1)
 
-    def op(self, kind, flags=0, M_in=0, M_out=0, K=0, Cin=0, Cout=0, eps=0.0, momentum=0.0, inp=(), out=()):
-        """appends an op; rows are lists (later ops patch earlier ones: statistics targets, epilogue reductions):
-        [kind, flags, M_in, M_out, K, Cin, Cout, eps, momentum, inp[N_IN], out[N_OUT], momentum2]"""
-        inp = list(inp) + [0] * (N_IN - len(inp))
-        out = list(out) + [0] * (N_OUT - len(out))
-        self.rows.append([kind, flags, M_in, M_out, K, Cin, Cout, eps, momentum, inp, out, 0.0])
-        return len(self.rows) - 1
+    def op(self, *args, **kwargs):
+        """appends an ``_Op`` and returns it"""
+        self.ops.append(_Op(*args, **kwargs))
+        return self.ops[-1]
 
 
 class _Arena(object):
@@ -146,16 +192,13 @@ class _Template(object):
     """op records with every static field filled in; row counts and tagged pointers are patched per scene"""
 
     def __init__(self, rec):
-        n = len(rec.rows)
+        ops = rec.ops
+        n = len(ops)
         self.arr = np.zeros(n, dtype=OP_DTYPE)
-        ptr = np.zeros((n, N_IN + N_OUT), dtype=np.uint64)          # inp | out
-        m_in = np.zeros(n, dtype=np.int64)
-        m_out = np.zeros(n, dtype=np.int64)
-        for i, r in enumerate(rec.rows):
-            self.arr[i] = (r[0], r[1], 0, 0, r[4], r[5], r[6], 0, r[7], r[8], r[11], 0, 0, 0)
-            m_in[i], m_out[i] = r[2], r[3]
-            ptr[i, :N_IN] = r[9]
-            ptr[i, N_IN:] = r[10]
+        for field in ("kind", "flags", "K", "Cin", "Cout", "eps", "momentum", "momentum2"):
+            self.arr[field] = [getattr(o, field) for o in ops]
+        ptr = np.array([o.inp + o.out for o in ops], dtype=np.uint64).reshape(n, N_IN + N_OUT)
+        m_in, m_out = (np.array([getattr(o, f) for o in ops], dtype=np.int64) for f in ("M_in", "M_out"))
         self.m_in_lit, self.m_out_lit = np.maximum(m_in, 0), np.maximum(m_out, 0)
         self.m_in_lvl, self.m_out_lvl = np.maximum(-m_in - 1, 0), np.maximum(-m_out - 1, 0)
         self.m_in_sym, self.m_out_sym = m_in < 0, m_out < 0
@@ -186,11 +229,8 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
-class _Table(object):
-    """gather tables of one conv as slots: forward (rows = outputs) and dIn (rows = inputs) + flip flag"""
-
-    def __init__(self, nbr_f=0, order_f=0, nbr_b=0, order_b=0, flip=0):
-        self.nbr_f, self.order_f, self.nbr_b, self.order_b, self.flip = nbr_f, order_f, nbr_b, order_b, flip
+# gather tables of one conv as slots: forward (rows = outputs) and dIn (rows = inputs) + flip flag
+_Table = collections.namedtuple("_Table", "nbr_f order_f nbr_b order_b flip", defaults=(0, 0, 0, 0, 0))
 
 
 def _subm(l):
@@ -205,9 +245,261 @@ def _up(l):
     return _Table(_TBL | (l * 6 + 4), _TBL | (l * 6 + 5), _TBL | (l * 6 + 2), _TBL | (l * 6 + 3), 0)
 
 
-class _Compiled(object):
-    """forward + backward templates of one (model, mode)"""
-    pass
+def _conv_dims(conv):
+    assert conv.bias is None, "the UNet convolutions carry no bias (sparse_unet3d.py)"
+    return int(np.prod(conv.kernel_size)), conv.in_channels, conv.out_channels
+
+
+class _TrainEmitter(object):
+    """the fp32 ops of a training or evaluation pass, with everything that lives for ONE recording: the three recorders,
+    the gradient handles, the profiler's entries, the statistics sources and the BatchNorm layers applied by their
+    consumer.  ``conv`` / ``bn_relu`` / ``cat`` return (out_handle, backward_closure): a hand-written tape, the closures
+    emit into the backward recorder when ``UNetProgram`` calls them in reverse."""
+
+    def __init__(self, synced):
+        self.rec, self.recb, self.prec = _Recorder(_FWD), _Recorder(_BWD), _Recorder(_PAR, align=16)
+        self.grad = {}
+        self.acc_f, self.acc_b, self.count = [], [], []
+        self.stats_src, self.fuse_stats = {}, _fuse_stats_enabled()
+        # virt: handle of a BatchNorm applied by its consumer -> (x, C, F_BN_IN | F_RELU, eps, (mean, var, gamma, beta))
+        self.virt, self.fuse_apply_lvl = {}, _fuse_apply_level()
+        self.fuse_fin = _fuse_fin_enabled() and self.fuse_stats
+        self.fuse_fin_lvl = int(os.environ.get("WSIS_FUSE_BN_FIN_LVL", "0"))      # (EXPERIMENTAL build: from this level on)
+        if synced:      # every BatchNorm layer stays an op of its own: _run_synced runs it between parts
+            self.fuse_fin, self.fuse_apply_lvl = False, 99
+
+    def grad_handle(self, p):
+        # parameter gradients live densely in their own flat buffer (one all-reduce for data parallelism)
+        if id(p) not in self.grad:
+            self.grad[id(p)] = self.prec.alloc(-1, p.numel())
+        return self.grad[id(p)]
+
+    def conv(self, x, conv, table, lvl_in, lvl_out, residual=0, stats=True):
+        rec, recb = self.rec, self.recb
+        K, Cin, Cout = _conv_dims(conv)
+        W = conv.weight
+        y = rec.alloc(lvl_out, Cout)
+        t = table if table is not None else _Table()
+        # BatchNorm statistics of the output from the convolution's own epilogue (training passes, layers on the
+        # wave-autonomous kernel): per-slice (sum, sum of squares) partials next to the output
+        part = 0
+        if stats and self.fuse_stats and sp_ops._use_fwd2(K, Cin, Cout):
+            part = rec.alloc(lvl_out, 2 * Cout, per_slice=True)
+        # the input may be a BatchNorm(+ReLU) that is applied while this convolution reads it (see bn_relu)
+        x, C_in, bn_flags, eps, bn_in = self.virt.get(x, (x, Cin, 0, 0.0, (0, 0, 0, 0)))
+        assert C_in == Cin and (not bn_flags or sp_ops._use_fwd2(K, Cin, Cout))
+        op = rec.op(OP_CONV, bn_flags | (F_STATS if part else 0), _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout, eps=eps,
+                    inp=(x, t.nbr_f, t.order_f, W.data_ptr(), 0, residual), out=(y, part))
+        op.inp[S_CONV.BN_IN] = bn_in
+        if part:
+            self.stats_src[y] = [(part, Cout, op)]
+        self.acc_f.append(("spconv_fwd_kernel", t.nbr_f, lvl_out, Cin, Cout))
+
+        def bwd(dy, need_dx=True):
+            dx = recb.alloc(lvl_in, Cin) if need_dx else 0
+            dW = self.grad_handle(W)
+            bop = recb.op(OP_CONV_BWD, bn_flags | (F_FLIP if t.flip else 0), _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout, eps=eps,
+                          inp=(x, W.data_ptr(), dy, t.nbr_f, t.order_f, t.nbr_b, t.order_b), out=(dx, dW))
+            bop.inp[S_CONV_BWD.BN_IN] = bn_in
+            if need_dx:
+                self.acc_b.append(("spconv_fwd_kernel", t.nbr_b, lvl_in, Cout, Cin))
+            self.acc_b.append(("spconv_dw_kernel", t.nbr_f, lvl_out, Cin, Cout))
+            return dx
+        return y, bwd
+
+    def bn_relu(self, x, bn, lvl, relu=True, fuse=False):
+        """BatchNorm1d(+ReLU).  ``fuse``: the only consumer is a convolution on the wave-autonomous kernel, which applies
+        the BatchNorm while it reads its input (the returned handle is virtual: nothing is written).  Training
+        statistics come from the producing convolutions' epilogue partials where they exist -- finished inside those
+        launches (F_STAT_FIN) or by a finalize op -- otherwise from a pass over x."""
+        rec, recb = self.rec, self.recb
+        C = bn.num_features
+        training = bn.training or not bn.track_running_stats
+        update = bn.training and bn.track_running_stats
+        flags = (F_RELU if relu else 0) | (F_TRAINING if training else 0) | (F_UPDATE if update else 0)
+        if update and bn.num_batches_tracked is not None:
+            assert bn.momentum is not None, "cumulative-average BatchNorm is not used by 3D-WSIS"
+            self.count.append(bn)
+        fuse = fuse and lvl >= self.fuse_apply_lvl and self.fuse_stats and C % 32 == 0
+        momentum = bn.momentum if bn.momentum is not None else 0.1
+        mean = rec.alloc(-1, C) if training else bn.running_mean.data_ptr()
+        var = rec.alloc(-1, C) if training else bn.running_var.data_ptr()
+        src = self.stats_src.get(x) if training else None
+        have_parts = src is not None and sum(c for _, c, _ in src) == C and len(src) <= 2
+        stats_done = False
+        if (have_parts and self.fuse_fin and lvl >= self.fuse_fin_lvl
+                and all(p.out[S_CONV.FIN1_MEAN] == 0 for _, _, p in src)):
+            # every producer finishes its channel range of this BatchNorm's statistics inside its own launch
+            c0 = 0
+            running = (_ptr(bn.running_mean), _ptr(bn.running_var)) if update else (0, 0)
+            for _, c, p in src:
+                tgt = [_at(h, c0) for h in (mean, var) + running]
+                if not (p.flags & F_STAT_FIN):
+                    p.flags |= F_STAT_FIN
+                    p.out[S_CONV.FIN0], p.inp[S_CONV.FIN0_RUNNING] = tgt[:2], tgt[2:]
+                    p.momentum = momentum
+                else:
+                    p.out[S_CONV.FIN1] = tgt
+                    p.momentum2 = momentum
+                c0 += c
+            stats_done = True
+        y = rec.alloc(lvl, 0 if fuse else C)
+        if fuse:
+            self.virt[y] = (x, C, F_BN_IN | (F_RELU if relu else 0), bn.eps, (mean, var, _ptr(bn.weight), _ptr(bn.bias)))
+        if training and not stats_done:
+            K0, parts, sflags = 0, (0, 0), flags
+            if have_parts:
+                sflags |= F_STATS            # the producers' epilogues wrote the partials: no statistics pass over x
+                K0 = src[0][1]
+                parts = (src[0][0], src[1][0] if len(src) == 2 else 0)
+            op = rec.op(OP_BN_RELU, sflags, _lvl(lvl), _lvl(lvl), K0, C, C, bn.eps, momentum,
+                        inp=(x, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var)),
+                        out=(0 if fuse else y, mean, var))
+            op.inp[S_BN.PARTS0], op.inp[S_BN.PARTS1] = parts
+            # algorithmic bytes of the op (bench.py's BatchNorm line): x read + y written; a statistics pass over x
+            # (no epilogue partials) reads x once more
+            self.acc_f.append(("bn_op", 0, lvl, C, (0 if fuse else 2) + (0 if have_parts else 1)))
+        elif not fuse:
+            # statistics known (finished by the producers, or evaluation mode): apply pass only
+            rec.op(OP_BN_RELU, flags & ~(F_TRAINING | F_UPDATE), _lvl(lvl), _lvl(lvl), 0, C, C, bn.eps, momentum,
+                   inp=(x, _ptr(bn.weight), _ptr(bn.bias), mean, var), out=(y,))
+            self.acc_f.append(("bn_op", 0, lvl, C, 2))
+
+        def bwd(dy, addend=0):
+            # ``addend``: gradient arriving at x over a second path (residual skip / UNet skip connection), added
+            # in the same pass instead of a separate accumulation kernel
+            dx = recb.alloc(lvl, C)
+            dg = self.grad_handle(bn.weight) if bn.weight is not None else recb.alloc(-1, C)
+            db = self.grad_handle(bn.bias) if bn.bias is not None else recb.alloc(-1, C)
+            recb.op(OP_BN_RELU_BWD, flags & ~F_STATS, _lvl(lvl), _lvl(lvl), 0, C, C, bn.eps, 0.0,      # (F_STATS: fuse_bn_bwd)
+                    inp=(x, dy, mean, var, _ptr(bn.weight), _ptr(bn.bias), addend), out=(dx, dg, db))
+            # x and dy read, dx written, the addend read where there is one (a separate reduction pass over x and dy,
+            # taken when the producing dIn pass left no partials, is not counted: algorithmic = the fused form)
+            self.acc_b.append(("bn_op", 0, lvl, C, 3 + (1 if addend else 0)))
+            return dx
+        return y, bwd
+
+    def cat(self, a, b, lvl, C0):
+        """[a | b] of C0 channels each; the closure splits the gradient: d -> (d_a, d_b)"""
+        rec, recb = self.rec, self.recb
+        cat = rec.alloc(lvl, 2 * C0)
+        rec.op(OP_CAT, 0, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(a, b), out=(cat,))
+        if a in self.stats_src and b in self.stats_src:      # statistics of a concatenation = both halves'
+            self.stats_src[cat] = self.stats_src[a] + self.stats_src[b]
+
+        def bwd(d):
+            d_a = recb.alloc(lvl, C0)
+            d_b = recb.alloc(lvl, C0)
+            recb.op(OP_SPLIT, 0, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(d,), out=(d_a, d_b))
+            return d_a, d_b
+        return cat, bwd
+
+    def fuse_bn_bwd(self):
+        """dIn passes whose output is the dy of a BatchNorm backward a few ops later (training mode, layer on the
+        wave-autonomous kernel) also write that op's (sum dz, sum dz*xhat) slice partials from their epilogue: both
+        ops get F_STATS and the BatchNorm op the partial buffer (WSIS_FUSE_BN_BWD=0: separate pass)"""
+        if os.environ.get("WSIS_FUSE_BN_BWD", "1") == "0" or not self.fuse_stats:
+            return
+        ops = self.recb.ops
+        for i, r in enumerate(ops):
+            dx = r.out[S_CONV_BWD.DX] if r.kind == OP_CONV_BWD else 0
+            if not dx or not sp_ops._use_fwd2(r.K, r.Cout, r.Cin):      # the dIn product gathers dY: roles of the channels swap
+                continue
+            for b in ops[i + 1:i + 5]:
+                if (b.kind == OP_BN_RELU_BWD and b.inp[S_BN_BWD.DY] == dx and (b.flags & F_TRAINING) and b.Cin == r.Cin
+                        and b.M_in == r.M_in):
+                    b.inp[S_BN_BWD.DIN_PARTS] = self.recb.alloc(-b.M_in - 1, 2 * r.Cin, per_slice=True)      # (_lvl undone)
+                    b.flags |= F_STATS
+                    r.flags |= F_STATS
+                    break
+
+
+class _LpEmitter(object):
+    """the 16-bit evaluation-mode forward (F_LP ops): a 16-bit activation of C channels is C / 2 floats per row of the
+    arena.  Running statistics only, BatchNorm applied by ops of its own (no statistics, no fused forms), no backward:
+    every closure is None."""
+
+    def __init__(self):
+        self.rec = _Recorder(_FWD)
+
+    def conv(self, x, conv, table, lvl_in, lvl_out, residual=0, stats=True):
+        K, Cin, Cout = _conv_dims(conv)
+        t = table if table is not None else _Table()
+        y = self.rec.alloc(lvl_out, Cout // 2)
+        # (the executor casts the fp32 weight to 16-bit B^T slices inside the call: the pass follows the optimizer;
+        # a skip path is added in the epilogue before its one rounding -- the walk adds two rounded tensors)
+        self.rec.op(OP_CONV, F_LP, _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
+                    inp=(x, t.nbr_f, t.order_f, conv.weight.data_ptr(), 0, residual), out=(y,))
+        return y, None
+
+    def bn_relu(self, x, bn, lvl, relu=True, fuse=False, out=0, out_f32=False):
+        """``out``: a tensor of the caller's instead of an allocation of the arena; ``out_f32``: stored as fp32"""
+        C = bn.num_features
+        y = out or self.rec.alloc(lvl, C if out_f32 else C // 2)
+        flags = F_LP | (F_RELU if relu else 0) | (F_OUT_F32 if out_f32 else 0)
+        self.rec.op(OP_BN_RELU, flags, _lvl(lvl), _lvl(lvl), 0, C, C, bn.eps, 0.0,
+                    inp=(x, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var)), out=(y,))
+        return y, None
+
+    def cat(self, a, b, lvl, C0):
+        cat = self.rec.alloc(lvl, C0)                  # 2 * C0 16-bit channels
+        self.rec.op(OP_CAT, F_LP, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(a, b), out=(cat,))
+        return cat, None
+
+
+# ---- the one walk of the module tree: ``em`` is an emitter, every step returns (out_handle, backward_closure); what the
+# closures do -- and whether anybody calls them -- is the emitter's business (the 16-bit program has no backward)
+def _residual_block(em, x, blk, lvl):
+    seq = blk.conv_branch
+    bn1, conv1, bn2, conv2 = seq[0], seq[2], seq[3], seq[5]
+    table = _subm(lvl)
+    a1, b_bn1 = em.bn_relu(x, bn1, lvl, fuse=True)
+    z1, b_c1 = em.conv(a1, conv1, table, lvl, lvl)
+    a2, b_bn2 = em.bn_relu(z1, bn2, lvl, fuse=True)
+    first = blk.i_branch[0]
+    if isinstance(first, nn.Identity):
+        res, b_i = x, None
+    else:
+        res, b_i = em.conv(x, first, None, lvl, lvl, stats=False)   # 1x1 projection of the skip path
+    out, b_c2 = em.conv(a2, conv2, table, lvl, lvl, residual=res)
+
+    def bwd(d_out):
+        d_a1 = b_c1(b_bn2(b_c2(d_out)))
+        d_skip = d_out if b_i is None else b_i(d_out)
+        return b_bn1(d_a1, addend=d_skip)
+    return out, bwd
+
+
+def _blocks(em, x, blocks, lvl):
+    bwds = []
+    for blk in blocks:
+        x, b = _residual_block(em, x, blk, lvl)
+        bwds.append(b)
+
+    def bwd(d):
+        for b in reversed(bwds):
+            d = b(d)
+        return d
+    return x, bwd
+
+
+def _ublock(em, x, ub, lvl):
+    x, b_head = _blocks(em, x, ub.blocks, lvl)
+    if len(ub.nPlanes) == 1:
+        return x, b_head
+    a, b_bn = em.bn_relu(x, ub.conv[0], lvl, fuse=True)
+    d, b_down = em.conv(a, ub.conv[2], _down(lvl), lvl, lvl + 1)
+    u, b_u = _ublock(em, d, ub.u, lvl + 1)
+    a2, b_bn2 = em.bn_relu(u, ub.deconv[0], lvl + 1, fuse=True)
+    up, b_up = em.conv(a2, ub.deconv[2], _up(lvl), lvl + 1, lvl)
+    cat, b_cat = em.cat(x, up, lvl, ub.nPlanes[0])
+    y, b_tail = _blocks(em, cat, ub.blocks_tail, lvl)
+
+    def bwd(d_y):
+        d_id, d_up = b_cat(b_tail(d_y))
+        d_a = b_down(b_u(b_bn2(b_up(d_up))))
+        return b_head(b_bn(d_a, addend=d_id))
+    return y, bwd
 
 
 class UNetProgram(object):
@@ -228,258 +520,17 @@ class UNetProgram(object):
         # gone; a 44 MB allocation + the cached views rebuilt per step, data-parallel exchange still in place).
         self.persistent_grads = os.environ.get("WSIS_PERSISTENT_GRADS", "1") != "0"
         self.bn_sync = None          # _BnSync while the model's BatchNorm layers share their statistics across ranks
-        self._cache = {}
+        self._cache = {}             # compiled programs by mode key
+        self.Mvec = self.table_lut = self.table_tensors = self.keep = None      # the scene's pyramid (bind)
 
-    # ---- symbolic recording: every helper returns (out_handle, backward_closure) -----------------------------
-    def _conv(self, rec, x, conv, table, lvl_in, lvl_out, residual=0, stats=True):
-        K = int(np.prod(conv.kernel_size))
-        Cin, Cout = conv.in_channels, conv.out_channels
-        W = conv.weight
-        assert conv.bias is None, "the UNet convolutions carry no bias (sparse_unet3d.py)"
-        y = rec.alloc(lvl_out, Cout)
-        t = table if table is not None else _Table()
-        # BatchNorm statistics of the output from the convolution's own epilogue (training passes, layers on the
-        # wave-autonomous kernel): per-slice (sum, sum of squares) partials next to the output
-        part = 0
-        if stats and self._fuse_stats and sp_ops._use_fwd2(K, Cin, Cout):
-            part = rec.alloc(lvl_out, 2 * Cout, per_slice=True)
-        # the input may be a BatchNorm(+ReLU) that is applied while this convolution reads it (see _bn_relu)
-        v = self._virt.get(x)
-        flags, eps, bn_in = (F_STATS if part else 0), 0.0, (0, 0, 0, 0)
-        if v is not None:
-            assert sp_ops._use_fwd2(K, Cin, Cout) and v["C"] == Cin
-            x = v["x"]
-            flags |= F_BN_IN | (F_RELU if v["relu"] else 0)
-            eps, bn_in = v["eps"], (v["mean"], v["var"], v["gamma"], v["beta"])
-        row = rec.op(OP_CONV, flags, _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout, eps=eps,
-                     inp=(x, t.nbr_f, t.order_f, W.data_ptr(), 0, residual) + bn_in, out=(y, part))
-        if part:
-            self._stats_src[y] = [(part, Cout, row)]
-        self._acc_f.append(("spconv_fwd_kernel", t.nbr_f, lvl_out, Cin, Cout))
-
-        def bwd(recb, dy, need_dx=True):
-            dx = recb.alloc(lvl_in, Cin) if need_dx else 0
-            dW = self._grad_handle(W)
-            bflags = (F_FLIP if t.flip else 0) | ((F_BN_IN | (F_RELU if v["relu"] else 0)) if v is not None else 0)
-            recb.op(OP_CONV_BWD, bflags, _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout, eps=eps,
-                    inp=(x, W.data_ptr(), dy, t.nbr_f, t.order_f, t.nbr_b, t.order_b) + bn_in, out=(dx, dW))
-            if need_dx:
-                self._acc_b.append(("spconv_fwd_kernel", t.nbr_b, lvl_in, Cout, Cin))
-            self._acc_b.append(("spconv_dw_kernel", t.nbr_f, lvl_out, Cin, Cout))
-            return dx
-        return y, bwd
-
-    def _bn_relu(self, rec, x, bn, lvl, relu=True, fuse=False):
-        """BatchNorm1d(+ReLU).  ``fuse``: the only consumer is a convolution on the wave-autonomous kernel, which applies
-        the BatchNorm while it reads its input (the returned handle is virtual: nothing is written).  Training
-        statistics come from the producing convolutions' epilogue partials where they exist -- finished inside those
-        launches (F_STAT_FIN) or by a finalize op -- otherwise from a pass over x."""
-        C = bn.num_features
-        training = bn.training or not bn.track_running_stats
-        update = bn.training and bn.track_running_stats
-        flags = (F_RELU if relu else 0) | (F_TRAINING if training else 0) | (F_UPDATE if update else 0)
-        if update and bn.num_batches_tracked is not None:
-            assert bn.momentum is not None, "cumulative-average BatchNorm is not used by 3D-WSIS"
-            self._count.append(bn)
-        fuse = fuse and lvl >= self._fuse_apply_lvl and self._fuse_stats and C % 32 == 0
-        momentum = bn.momentum if bn.momentum is not None else 0.1
-        mean = rec.alloc(-1, C) if training else bn.running_mean.data_ptr()
-        var = rec.alloc(-1, C) if training else bn.running_var.data_ptr()
-        src = self._stats_src.get(x) if training else None
-        have_parts = src is not None and sum(c for _, c, _ in src) == C and len(src) <= 2
-        stats_done = False
-        if have_parts and self._fuse_fin and lvl >= self._fuse_fin_lvl and all(rec.rows[r][10][4] == 0 for _, _, r in src):
-            # every producer finishes its channel range of this BatchNorm's statistics inside its own launch
-            c0 = 0
-            rm = _ptr(bn.running_mean) if update else 0
-            rv = _ptr(bn.running_var) if update else 0
-            for _, c, r in src:
-                row = rec.rows[r]
-                tgt = (_at(mean, c0), _at(var, c0), _at(rm, c0), _at(rv, c0))
-                if not (row[1] & F_STAT_FIN):
-                    row[1] |= F_STAT_FIN
-                    row[10][2], row[10][3], row[9][10], row[9][11] = tgt
-                    row[8] = momentum
-                else:
-                    row[10][4:8] = tgt
-                    row[11] = momentum
-                c0 += c
-            stats_done = True
-        y = rec.alloc(lvl, 0 if fuse else C)
-        if fuse:
-            self._virt[y] = dict(x=x, C=C, mean=mean, var=var, gamma=_ptr(bn.weight), beta=_ptr(bn.bias), eps=bn.eps,
-                                 relu=relu)
-        if training and not stats_done:
-            K0, parts, sflags = 0, (0, 0), flags
-            if have_parts:
-                sflags |= F_STATS            # the producers' epilogues wrote the partials: no statistics pass over x
-                K0 = src[0][1]
-                parts = (src[0][0], src[1][0] if len(src) == 2 else 0)
-            rec.op(OP_BN_RELU, sflags, _lvl(lvl), _lvl(lvl), K0, C, C, bn.eps, momentum,
-                   inp=(x, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var), parts[0], parts[1]),
-                   out=(0 if fuse else y, mean, var))
-            # algorithmic bytes of the op (bench.py's BatchNorm line): x read + y written; a statistics pass over x
-            # (no epilogue partials) reads x once more
-            self._acc_f.append(("bn_op", 0, lvl, C, (0 if fuse else 2) + (0 if have_parts else 1)))
-        elif not fuse:
-            # statistics known (finished by the producers, or evaluation mode): apply pass only
-            rec.op(OP_BN_RELU, flags & ~(F_TRAINING | F_UPDATE), _lvl(lvl), _lvl(lvl), 0, C, C, bn.eps, momentum,
-                   inp=(x, _ptr(bn.weight), _ptr(bn.bias), mean, var), out=(y,))
-            self._acc_f.append(("bn_op", 0, lvl, C, 2))
-
-        def bwd(recb, dy, addend=0):
-            # ``addend``: gradient arriving at x over a second path (residual skip / UNet skip connection), added
-            # in the same pass instead of a separate accumulation kernel
-            dx = recb.alloc(lvl, C)
-            dg = self._grad_handle(bn.weight) if bn.weight is not None else recb.alloc(-1, C)
-            db = self._grad_handle(bn.bias) if bn.bias is not None else recb.alloc(-1, C)
-            recb.op(OP_BN_RELU_BWD, flags & ~F_STATS, _lvl(lvl), _lvl(lvl), 0, C, C, bn.eps, 0.0,      # (F_STATS: _fuse_bn_bwd)
-                    inp=(x, dy, mean, var, _ptr(bn.weight), _ptr(bn.bias), addend), out=(dx, dg, db))
-            # x and dy read, dx written, the addend read where there is one (a separate reduction pass over x and dy,
-            # taken when the producing dIn pass left no partials, is not counted: algorithmic = the fused form)
-            self._acc_b.append(("bn_op", 0, lvl, C, 3 + (1 if addend else 0)))
-            return dx
-        return y, bwd
-
-    def _fuse_bn_bwd(self, recb):
-        """dIn passes whose output is the dy of a BatchNorm backward a few ops later (training mode, layer on the
-        wave-autonomous kernel) also write that op's (sum dz, sum dz*xhat) slice partials from their epilogue: both
-        ops get F_STATS and the BatchNorm op the partial buffer in inp[7] (WSIS_FUSE_BN_BWD=0: separate pass)"""
-        if os.environ.get("WSIS_FUSE_BN_BWD", "1") == "0" or not self._fuse_stats:
-            return
-        rows = recb.rows
-        for i, r in enumerate(rows):
-            if r[0] != OP_CONV_BWD or not r[10][0]:
-                continue
-            K, Cin, Cout = r[4], r[5], r[6]
-            if not sp_ops._use_fwd2(K, Cout, Cin):          # the dIn product gathers dY: roles of the channels swap
-                continue
-            dx = r[10][0]
-            for j in range(i + 1, min(i + 5, len(rows))):
-                b = rows[j]
-                if b[0] == OP_BN_RELU_BWD and b[9][1] == dx and (b[1] & F_TRAINING) and b[5] == Cin and b[2] == r[2]:
-                    lvl = -b[2] - 1
-                    b[9][7] = recb.alloc(lvl, 2 * Cin, per_slice=True)
-                    b[1] |= F_STATS
-                    r[1] |= F_STATS
-                    break
-
-    def _residual_block(self, rec, x, blk, lvl):
-        seq = blk.conv_branch
-        bn1, conv1, bn2, conv2 = seq[0], seq[2], seq[3], seq[5]
-        table = _subm(lvl)
-        a1, b_bn1 = self._bn_relu(rec, x, bn1, lvl, fuse=True)
-        z1, b_c1 = self._conv(rec, a1, conv1, table, lvl, lvl)
-        a2, b_bn2 = self._bn_relu(rec, z1, bn2, lvl, fuse=True)
-        first = blk.i_branch[0]
-        if isinstance(first, nn.Identity):
-            res, b_i = x, None
-        else:
-            res, b_i = self._conv(rec, x, first, None, lvl, lvl, stats=False)   # 1x1 projection of the skip path
-        out, b_c2 = self._conv(rec, a2, conv2, table, lvl, lvl, residual=res)
-
-        def bwd(recb, d_out):
-            d_a2 = b_c2(recb, d_out)
-            d_z1 = b_bn2(recb, d_a2)
-            d_a1 = b_c1(recb, d_z1)
-            d_skip = d_out if b_i is None else b_i(recb, d_out)
-            return b_bn1(recb, d_a1, addend=d_skip)
-        return out, bwd
-
-    def _ublock(self, rec, x, ub, lvl):
-        bwds = []
-        for blk in ub.blocks:
-            x, b = self._residual_block(rec, x, blk, lvl)
-            bwds.append(b)
-        if len(ub.nPlanes) == 1:
-            def bwd_leaf(recb, d):
-                for b in reversed(bwds):
-                    d = b(recb, d)
-                return d
-            return x, bwd_leaf
-        C0 = ub.nPlanes[0]
-        identity = x
-        a, b_bn = self._bn_relu(rec, x, ub.conv[0], lvl, fuse=True)
-        d, b_down = self._conv(rec, a, ub.conv[2], _down(lvl), lvl, lvl + 1)
-        u, b_u = self._ublock(rec, d, ub.u, lvl + 1)
-        a2, b_bn2 = self._bn_relu(rec, u, ub.deconv[0], lvl + 1, fuse=True)
-        up, b_up = self._conv(rec, a2, ub.deconv[2], _up(lvl), lvl + 1, lvl)
-        cat = rec.alloc(lvl, 2 * C0)
-        rec.op(OP_CAT, 0, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(identity, up), out=(cat,))
-        if identity in self._stats_src and up in self._stats_src:      # statistics of a concatenation = both halves'
-            self._stats_src[cat] = self._stats_src[identity] + self._stats_src[up]
-        x = cat
-        tails = []
-        for blk in ub.blocks_tail:
-            x, b = self._residual_block(rec, x, blk, lvl)
-            tails.append(b)
-
-        def bwd(recb, dcur):
-            for b in reversed(tails):
-                dcur = b(recb, dcur)
-            d_id = recb.alloc(lvl, C0)
-            d_up = recb.alloc(lvl, C0)
-            recb.op(OP_SPLIT, 0, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(dcur,), out=(d_id, d_up))
-            d_a2 = b_up(recb, d_up)
-            d_u = b_bn2(recb, d_a2)
-            d_d = b_u(recb, d_u)
-            d_a = b_down(recb, d_d)
-            d_x = b_bn(recb, d_a, addend=d_id)
-            for b in reversed(bwds):
-                d_x = b(recb, d_x)
-            return d_x
-        return x, bwd
-
-    # ---- the 16-bit evaluation-mode forward (F_LP ops): a 16-bit activation of C channels is C / 2 floats per row of the
-    # arena.  Running statistics only, BatchNorm applied by ops of its own (no statistics, no fused forms), no backward.
-    def _lp_conv(self, rec, x, conv, table, lvl_in, lvl_out, residual=0):
-        K = int(np.prod(conv.kernel_size))
-        Cin, Cout = conv.in_channels, conv.out_channels
-        assert conv.bias is None, "the UNet convolutions carry no bias (sparse_unet3d.py)"
-        t = table if table is not None else _Table()
-        y = rec.alloc(lvl_out, Cout // 2)
-        # (the executor casts the fp32 weight to 16-bit B^T slices inside the call: the pass follows the optimizer)
-        rec.op(OP_CONV, F_LP, _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
-               inp=(x, t.nbr_f, t.order_f, conv.weight.data_ptr(), 0, residual), out=(y,))
-        return y
-
-    def _lp_bn_relu(self, rec, x, bn, lvl, relu=True, out_f32=False):
-        C = bn.num_features
-        y = rec.alloc(lvl, C if out_f32 else C // 2)
-        flags = F_LP | (F_RELU if relu else 0) | (F_OUT_F32 if out_f32 else 0)
-        rec.op(OP_BN_RELU, flags, _lvl(lvl), _lvl(lvl), 0, C, C, bn.eps, 0.0,
-               inp=(x, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var)), out=(y,))
-        return y
-
-    def _lp_residual_block(self, rec, x, blk, lvl):
-        seq = blk.conv_branch
-        bn1, conv1, bn2, conv2 = seq[0], seq[2], seq[3], seq[5]
-        table = _subm(lvl)
-        a1 = self._lp_bn_relu(rec, x, bn1, lvl)
-        z1 = self._lp_conv(rec, a1, conv1, table, lvl, lvl)
-        a2 = self._lp_bn_relu(rec, z1, bn2, lvl)
-        first = blk.i_branch[0]
-        res = x if isinstance(first, nn.Identity) else self._lp_conv(rec, x, first, None, lvl, lvl)
-        # the skip path is added in conv2's epilogue before its one rounding (the walk adds two rounded tensors)
-        return self._lp_conv(rec, a2, conv2, table, lvl, lvl, residual=res)
-
-    def _lp_ublock(self, rec, x, ub, lvl):
-        for blk in ub.blocks:
-            x = self._lp_residual_block(rec, x, blk, lvl)
-        if len(ub.nPlanes) == 1:
-            return x
-        C0 = ub.nPlanes[0]
-        a = self._lp_bn_relu(rec, x, ub.conv[0], lvl)
-        d = self._lp_conv(rec, a, ub.conv[2], _down(lvl), lvl, lvl + 1)
-        u = self._lp_ublock(rec, d, ub.u, lvl + 1)
-        a2 = self._lp_bn_relu(rec, u, ub.deconv[0], lvl + 1)
-        up = self._lp_conv(rec, a2, ub.deconv[2], _up(lvl), lvl + 1, lvl)
-        cat = rec.alloc(lvl, C0)                  # 2 * C0 16-bit channels
-        rec.op(OP_CAT, F_LP, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(x, up), out=(cat,))
-        x = cat
-        for blk in ub.blocks_tail:
-            x = self._lp_residual_block(rec, x, blk, lvl)
-        return x
+    # ---- compile (once per mode) / bind (per scene) ------------------------------------------------------------
+    def _cached(self, key, record):
+        c = self._cache.get(key)
+        if c is None:
+            if len(self._cache) > 8:
+                self._cache.clear()
+            c = self._cache[key] = record()
+        return c
 
     def compiled_lp(self, dtype, out_f32):
         """the 16-bit evaluation-mode forward program of ``dtype`` (bf16 / fp16); ``out_f32``: the output layer's
@@ -489,99 +540,65 @@ class UNetProgram(object):
         key = ("lp", dtype, bool(out_f32), tuple((p.data_ptr(), p.dtype) for p in self.params),
                tuple((_ptr(bn.running_mean), _ptr(bn.running_var), bn.running_var.dtype if bn.running_var is not None
                       else None) for bn in self.bns))
-        c = self._cache.get(key)
-        if c is not None:
-            return c
-        if len(self._cache) > 8:
-            self._cache.clear()
+        return self._cached(key, lambda: self._record_lp(dtype, out_f32))
+
+    def _record_lp(self, dtype, out_f32):
         net = self.net
         dev = net.input_conv[0].weight.device
         if not lp_params_fp32(net, dev):
             raise ValueError("the 16-bit native pass reads the model's parameters and running statistics as contiguous "
                              "fp32 tensors (lp_params_fp32); a model with 16-bit parameters walks the modules")
-        rec = _Recorder(_FWD)
+        em = _LpEmitter()
+        rec = em.rec
         # the 6 -> 32 input convolution lies outside the 16-bit domain: the fp32 op, its output rounded once (what the
         # module walk's fallback does, spconv.ops._forward_lp)
         conv0 = net.input_conv[0]
-        K0, C0 = int(np.prod(conv0.kernel_size)), conv0.out_channels
+        K0, Cin0, C0 = _conv_dims(conv0)
         t0 = _subm(0)
         y32 = rec.alloc(0, C0)
-        rec.op(OP_CONV, 0, _lvl(0), _lvl(0), K0, conv0.in_channels, C0,
+        rec.op(OP_CONV, 0, _lvl(0), _lvl(0), K0, Cin0, C0,
                inp=(_EXT | 0, t0.nbr_f, t0.order_f, conv0.weight.data_ptr(), 0, 0), out=(y32,))
         y = rec.alloc(0, C0 // 2)
         rec.op(OP_CAST_LP, F_LP, _lvl(0), _lvl(0), 0, C0, C0, inp=(y32,), out=(y,))
-        y = self._lp_ublock(rec, y, net.unet, 0)
-        bn = net.output_layer[0]
-        C = bn.num_features
-        rec.op(OP_BN_RELU, F_LP | F_RELU | (F_OUT_F32 if out_f32 else 0), _lvl(0), _lvl(0), 0, C, C, bn.eps, 0.0,
-               inp=(y, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var)), out=(_EXT | 1,))
-        c = _Compiled()
+        y, _ = _ublock(em, y, net.unet, 0)
+        em.bn_relu(y, net.output_layer[0], 0, out=_EXT | 1, out_f32=out_f32)
+        c = types.SimpleNamespace()      # forward + backward templates of one (model, mode)
         c.fwd, c.fwd_arena = _Template(rec), _Arena(rec)
         c.fwd.arr["reserved"] = np.where((c.fwd.arr["flags"] & F_LP) != 0, sp_ops._LP_DTYPES[dtype], 0)
-        c.out_channels = C
-        self._cache[key] = c
+        c.out_channels = net.output_layer[0].num_features
         return c
 
-    def _grad_handle(self, p):
-        # parameter gradients live densely in their own flat buffer (one all-reduce for data parallelism)
-        h = self._grad.get(id(p))
-        if h is None:
-            h = self._prec.alloc(-1, p.numel())
-            self._grad[id(p)] = h
-        return h
-
-    # ---- compile (once per mode) / bind (per scene) ------------------------------------------------------------
     def _mode_key(self, need_dx):
         # bn_sync: the synced pass intercepts training-mode BatchNorm ops only -- the forms that finish the statistics
         # inside the producing convolution or apply them inside the consuming one leave no such op, so a program
         # compiled with them must never serve a synced pass (and the other way round)
         return (need_dx, self.bn_sync is not None, _fuse_stats_enabled(), _fuse_fin_enabled(), _fuse_apply_level(),
-                os.environ.get("WSIS_FUSE_BN_FIN_LVL", "0"),
+                os.environ.get("WSIS_FUSE_BN_FIN_LVL", "0"), os.environ.get("WSIS_FUSE_BN_BWD", "1"),
                 os.environ.get("WSIS_FWD2", "1"), tuple(bn.training for bn in self.bns), tuple(p.data_ptr() for p in self.params),
                 tuple(bn.running_mean.data_ptr() if bn.running_mean is not None else 0 for bn in self.bns))
 
     def compiled(self, need_dx):
-        key = self._mode_key(need_dx)
-        c = self._cache.get(key)
-        if c is not None:
-            return c
-        if len(self._cache) > 8:
-            self._cache.clear()
+        return self._cached(self._mode_key(need_dx), lambda: self._record(need_dx))
+
+    def _record(self, need_dx):
         net = self.net
-        c = _Compiled()
-        rec, recb = _Recorder(_FWD), _Recorder(_BWD)
-        self._prec, self._grad = _Recorder(_PAR, align=16), {}
-        self._acc_f, self._acc_b, self._count = [], [], []
-        self._stats_src, self._fuse_stats = {}, _fuse_stats_enabled()
-        self._virt, self._fuse_apply_lvl = {}, _fuse_apply_level()
-        self._fuse_fin = _fuse_fin_enabled() and self._fuse_stats
-        self._fuse_fin_lvl = int(os.environ.get("WSIS_FUSE_BN_FIN_LVL", "0"))      # (EXPERIMENTAL build: from this level on)
-        if self.bn_sync is not None:      # every BatchNorm layer stays an op of its own: _run_synced runs it between parts
-            self._fuse_fin, self._fuse_apply_lvl = False, 99
-        y, b_in = self._conv(rec, _EXT | 0, net.input_conv[0], _subm(0), 0, 0)
-        y, b_u = self._ublock(rec, y, net.unet, 0)
-        out, b_out = self._bn_relu(rec, y, net.output_layer[0], 0)
-        d = b_out(recb, _EXT | 1)
-        d = b_u(recb, d)
-        dx = b_in(recb, d, need_dx)
-        self._fuse_bn_bwd(recb)
-        c.fwd, c.bwd = _Template(rec), _Template(recb)
-        c.fwd_arena, c.bwd_arena, c.par_arena = _Arena(rec), _Arena(recb), _Arena(self._prec)
+        em = _TrainEmitter(synced=self.bn_sync is not None)
+        y, b_in = em.conv(_EXT | 0, net.input_conv[0], _subm(0), 0, 0)
+        y, b_u = _ublock(em, y, net.unet, 0)
+        out, b_out = em.bn_relu(y, net.output_layer[0], 0)
+        dx = b_in(b_u(b_out(_EXT | 1)), need_dx)
+        em.fuse_bn_bwd()
+        c = types.SimpleNamespace()      # forward + backward templates of one (model, mode)
+        c.fwd, c.bwd = _Template(em.rec), _Template(em.recb)
+        c.fwd_arena, c.bwd_arena, c.par_arena = _Arena(em.rec), _Arena(em.recb), _Arena(em.prec)
         c.out_id, c.dx_id = out & _ID_MASK, (dx & _ID_MASK) if need_dx else -1
-        c.grad_ids = [(self._grad[id(p)] & _ID_MASK) if id(p) in self._grad else -1 for p in self.params]
-        c.acc_f, c.acc_b, c.count = self._acc_f, self._acc_b, self._count
+        c.grad_ids = [(em.grad[id(p)] & _ID_MASK) if id(p) in em.grad else -1 for p in self.params]
+        c.acc_f, c.acc_b, c.count = em.acc_f, em.acc_b, em.count
         # milestone of the backward list: the op after which the first ~half of the flat parameter-gradient buffer is
         # final (gradients are allocated in the order the backward pass produces them)
-        done = np.zeros(len(recb.rows), dtype=np.int64)
-        hw = 0
-        for i, r in enumerate(recb.rows):
-            for h in r[10]:
-                if h & _PAR:
-                    hw = max(hw, (h & _ID_MASK) + 1)
-            done[i] = hw
-        c.bwd_grads_done = done
+        last = [max([(h & _ID_MASK) + 1 for h in o.out if h & _PAR] or [0]) for o in em.recb.ops]
+        c.bwd_grads_done = np.maximum.accumulate(np.array(last, dtype=np.int64))
         c.out_channels = net.output_layer[0].num_features
-        self._cache[key] = c
         return c
 
     def bind(self, tensor):
@@ -652,6 +669,13 @@ def _arena_tensor(nbytes, device, zero=False):
     return t, (t.data_ptr() + 255) // 256 * 256
 
 
+def _luts(fwd, tables, ext0, ext1, bwd=None, par=None):
+    """look-up tables of ``_Template.instantiate``: arena bases per allocation id, table pointers, the two external tensors"""
+    none = fwd[:0]
+    return {_FWD: fwd, _BWD: none if bwd is None else bwd, _PAR: none if par is None else par, _TBL: tables,
+            _EXT: np.array([ext0, ext1], dtype=np.uint64)}
+
+
 def _view(arena, base, offset, shape):
     numel = int(np.prod(shape))
     off = base + int(offset) - arena.data_ptr()
@@ -703,9 +727,7 @@ class UNetFunction(Function):
         offs, total = c.fwd_arena.layout(Mvec)
         arena, base = _arena_tensor(total, x.device)
         fwd_lut = offs.astype(np.uint64) + np.uint64(base)
-        none = fwd_lut[:0]
-        luts = {_FWD: fwd_lut, _TBL: table_lut, _EXT: np.array([x.data_ptr(), 0], dtype=np.uint64), _BWD: none,
-                _PAR: none}
+        luts = _luts(fwd_lut, table_lut, x.data_ptr(), 0)
         sy = prog.bn_sync.new_pass() if prog.bn_sync is not None else None      # row counts / arenas belong to THIS pass
         if sy is not None:
             sy.arenas = [arena]
@@ -742,8 +764,8 @@ class UNetFunction(Function):
         if not prog.persistent_grads or any(p.grad is not None for p in ga.params):
             ga = _GradArena(prog, c, poffs, ptotal, tail, dev)
         parena, pflat, first = ga.arena, ga.flat, ga.first
-        luts = {_FWD: ctx.fwd_lut, _BWD: boffs.astype(np.uint64) + np.uint64(gbase), _PAR: ga.lut, _TBL: ctx.table_lut,
-                _EXT: np.array([ctx.x.data_ptr(), d_out.data_ptr()], dtype=np.uint64)}
+        luts = _luts(ctx.fwd_lut, ctx.table_lut, ctx.x.data_ptr(), d_out.data_ptr(),
+                     bwd=boffs.astype(np.uint64) + np.uint64(gbase), par=ga.lut)
         hook = prog.overlap
         if ctx.sy is not None:
             ctx.sy.arenas = [ctx.arena, garena, parena]
@@ -809,21 +831,23 @@ def _bn_fwd_synced(lib, op, sy, dev, st, slot):
     M, C, flags = int(op["M_in"]), int(op["Cin"]), int(op["flags"])
     inp, out = [int(v) for v in op["inp"]], [int(v) for v in op["out"]]
     mom, eps = float(op["momentum"]), float(op["eps"])
-    mean, var = sy.view(out[1], C), sy.view(out[2], C)
+    x, y, p_mean, p_var = inp[S_BN.X], out[S_BN.Y], out[S_BN.MEAN], out[S_BN.VAR]
+    parts0, parts1 = inp[S_BN.PARTS0], inp[S_BN.PARTS1]
+    mean, var = sy.view(p_mean, C), sy.view(p_var, C)
     if M > 0 and (flags & F_STATS):
         n_part = (M + 31) // 32
-        C0 = int(op["K"]) if inp[6] else C
+        C0 = int(op["K"]) if parts1 else C
         wsb = lib.wsis_bn_stats_finalize_workspace_bytes(n_part, C)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _n.check(lib.wsis_bn_stats_finalize(inp[5], n_part, M, C0, out[1], out[2], None, None, mom, _n.ptr(ws), wsb, slot, st),
+        _n.check(lib.wsis_bn_stats_finalize(parts0, n_part, M, C0, p_mean, p_var, None, None, mom, _n.ptr(ws), wsb, slot, st),
                  "bn_stats_finalize")
-        if inp[6]:
-            _n.check(lib.wsis_bn_stats_finalize(inp[6], n_part, M, C - C0, out[1] + 4 * C0, out[2] + 4 * C0, None, None, mom,
+        if parts1:
+            _n.check(lib.wsis_bn_stats_finalize(parts1, n_part, M, C - C0, p_mean + 4 * C0, p_var + 4 * C0, None, None, mom,
                                                 _n.ptr(ws), wsb, slot, st), "bn_stats_finalize")
     elif M > 0:
         wsb = lib.wsis_bn_workspace_bytes(M, C)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _n.check(lib.wsis_bn_stats(inp[0], M, C, out[1], out[2], None, None, mom, _n.ptr(ws), wsb, st), "bn_stats")
+        _n.check(lib.wsis_bn_stats(x, M, C, p_mean, p_var, None, None, mom, _n.ptr(ws), wsb, st), "bn_stats")
     else:
         mean.zero_()
         var.zero_()
@@ -839,37 +863,40 @@ def _bn_fwd_synced(lib, op, sy, dev, st, slot):
     mean.copy_(mean64.float())
     var.copy_(var64.float())
     if flags & F_UPDATE:
-        rm, rv = sy.by_ptr[inp[3]], sy.by_ptr[inp[4]]
+        rm, rv = sy.by_ptr[inp[S_BN.RMEAN]], sy.by_ptr[inp[S_BN.RVAR]]
         unb = var64 * (N / (N - 1.0).clamp_min(1.0))
         rm.mul_(1.0 - mom).add_(mean, alpha=mom)
         rv.mul_(1.0 - mom).add_(unb.float(), alpha=mom)
-    sy.counts[out[1]] = N
-    if out[0] and M > 0:
-        _n.check(lib.wsis_bn_apply(inp[0], out[1], out[2], inp[1] or None, inp[2] or None, eps, 1 if flags & F_RELU else 0,
-                                   out[0], M, C, st), "bn_apply")
+    sy.counts[p_mean] = N
+    if y and M > 0:
+        _n.check(lib.wsis_bn_apply(x, p_mean, p_var, inp[S_BN.GAMMA] or None, inp[S_BN.BETA] or None, eps,
+                                   1 if flags & F_RELU else 0, y, M, C, st), "bn_apply")
 
 
 def _bn_bwd_synced(lib, op, sy, dev, st):
     import torch.distributed as dist
+    S = S_BN_BWD
     M, C, flags = int(op["M_in"]), int(op["Cin"]), int(op["flags"])
     inp, out = [int(v) for v in op["inp"]], [int(v) for v in op["out"]]
     eps, relu = float(op["eps"]), 1 if flags & F_RELU else 0
-    dg, db = sy.view(out[1], C), sy.view(out[2], C)
+    # x, dy, mean, var, gamma, beta: the leading arguments of both kernels
+    args = (inp[S.X], inp[S.DY], inp[S.MEAN], inp[S.VAR], inp[S.GAMMA] or None, inp[S.BETA] or None)
+    dg, db = sy.view(out[S.DGAMMA], C), sy.view(out[S.DBETA], C)
     if M > 0:
         wsb = lib.wsis_bn_workspace_bytes(M, C)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _n.check(lib.wsis_bn_bwd(inp[0], inp[1], inp[2], inp[3], inp[4] or None, inp[5] or None, eps, relu, 1, None, out[1],
-                                 out[2], None, M, C, _n.ptr(ws), wsb, st), "bn_bwd")
+        _n.check(lib.wsis_bn_bwd(*args, eps, relu, 1, None, out[S.DGAMMA], out[S.DBETA], None, M, C, _n.ptr(ws), wsb, st),
+                 "bn_bwd")
     else:
         dg.zero_()
         db.zero_()
     g = torch.cat((dg, db)).double()
     dist.all_reduce(g, group=sy.group)
-    N = sy.counts[inp[2]]
+    N = sy.counts[inp[S.MEAN]]
     if M > 0:
         sc = (g * (float(M) / N)).float()      # the kernel divides by the local row count
-        _n.check(lib.wsis_bn_bwd_apply(inp[0], inp[1], inp[2], inp[3], inp[4] or None, inp[5] or None, _n.ptr(sc[:C]),
-                                       _n.ptr(sc[C:]), eps, relu, out[0], inp[6] or None, M, C, st), "bn_bwd_apply")
+        _n.check(lib.wsis_bn_bwd_apply(*args, _n.ptr(sc[:C]), _n.ptr(sc[C:]), eps, relu, out[S.DX], inp[S.ADDEND] or None,
+                                       M, C, st), "bn_bwd_apply")
 
 
 def _run_synced(lib, ops, device, sy):
@@ -1022,16 +1049,21 @@ def lp_out_dtype(compute_dtype, autocast):
     return compute_dtype
 
 
+def _program(net):
+    """the model's UNetProgram (made on first use, kept on the model)"""
+    prog = getattr(net, "_native_prog", None)
+    if prog is None:
+        prog = net._native_prog = UNetProgram(net)
+    return prog
+
+
 def run_unet_lp(net, input_tensor, dtype, out_dtype):
     """the 16-bit evaluation-mode forward of input_conv + unet + output_layer (no gradient): features -> [M0, m] of
     ``out_dtype`` (``dtype`` or fp32).  The input features are rounded to ``dtype`` and widened, exactly what the walk's
     input convolution reads; every 16-bit value of the pass is rounded once (input convolution output, convolution
     epilogues after the residual, BatchNorm applies), concatenations copy bits."""
     _check_experimental_switches()
-    prog = getattr(net, "_native_prog", None)
-    if prog is None:
-        prog = UNetProgram(net)
-        net._native_prog = prog
+    prog = _program(net)
     prog.bind(input_tensor)
     x = input_tensor.features
     _n.require_cuda(x)
@@ -1041,9 +1073,7 @@ def run_unet_lp(net, input_tensor, dtype, out_dtype):
     offs, total = c.fwd_arena.layout(Mvec)
     arena, base = _arena_tensor(total, x.device)
     out = torch.empty((int(Mvec[0]), c.out_channels), dtype=out_dtype, device=x.device)
-    none = np.zeros(0, dtype=np.uint64)
-    luts = {_FWD: offs.astype(np.uint64) + np.uint64(base), _TBL: prog.table_lut,
-            _EXT: np.array([x.data_ptr(), out.data_ptr()], dtype=np.uint64), _BWD: none, _PAR: none}
+    luts = _luts(offs.astype(np.uint64) + np.uint64(base), prog.table_lut, x.data_ptr(), out.data_ptr())
     _run(_n.hip(), c.fwd.instantiate(Mvec, luts), x.device)
     sp_ops.verify_pending_counts()
     return out
@@ -1053,10 +1083,7 @@ def run_unet(net, input_tensor, sync_group=None):
     """input_conv + unet + output_layer of ``net`` on ``input_tensor`` (SparseConvTensor) -> features [M0, m].
     ``sync_group``: the process group the BatchNorm layers take their batch statistics over (None: per rank)"""
     _check_experimental_switches()
-    prog = getattr(net, "_native_prog", None)
-    if prog is None:
-        prog = UNetProgram(net)
-        net._native_prog = prog
+    prog = _program(net)
     if sync_group is None:
         prog.bn_sync = None
     elif prog.bn_sync is None or prog.bn_sync.group is not sync_group:

@@ -1,0 +1,203 @@
+"""unet_program_golden.npz: what ``model/unet_native.py`` records for the sparse UNet, as the executor would receive it.
+
+``UNetProgram.compiled`` / ``.compiled_lp`` turn the module tree into ``wsis_op`` templates; nothing of that needs a
+device.  For every case of ``CASES`` this file instantiates the templates with a fixed pyramid (``MVEC``) and fake
+look-up tables and keeps
+
+  fwd, bwd                 the instantiated op arrays as raw bytes (every field of every op)
+  *_offs, *_total          the three arena layouts
+  ids                      out_id, dx_id, out_channels
+  grad_ids, grads_done     the parameter-gradient ids and the backward list's milestone vector
+  acc_f, acc_b             the profiler's entries (kernel name as a code of ``ACC_NAMES``)
+  count                    the BatchNorm layers whose batch counter a pass advances, as indices into ``prog.bns``
+
+The fake bases are distinct per tag and lie in [2^40, 2^44), where no host allocation lies; every other non-zero
+pointer of an op must point into exactly one parameter or buffer of the model and is rewritten as
+``PARAM_TAG | index in sorted-name order << 32 | byte offset`` (fused statistics point into the middle of running_mean /
+running_var), so the arrays do not depend on where the process allocated the model.
+
+Only the surface of the recorder that its callers use is touched (``compiled``, ``compiled_lp``, ``instantiate``,
+``layout`` and the attributes of a compiled program), so the file can be run against any revision of
+``unet_native.py``: tests/test_unet_program_host.py pins later revisions to what the fixture's revision recorded.
+
+    WSIS_EXPERIMENTAL=1 python __graft_entry__.py && python tests/golden/make_unet_program_golden.py
+
+(the EXPERIMENTAL build records all 15 cases; rebuild the default flavour afterwards)
+"""
+import contextlib
+import importlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+FIXTURE = os.path.join(HERE, "unet_program_golden.npz")
+
+MVEC = (5000, 1200, 300, 80, 20)
+FAKE_LO, FAKE_HI = 1 << 40, 1 << 44
+PARAM_TAG = 1 << 56
+ACC_NAMES = {"spconv_fwd_kernel": 0, "spconv_dw_kernel": 1, "bn_op": 2}
+# every switch a case may set: cleared around each recording, so the caller's environment does not leak in
+SWITCHES = ("WSIS_FUSE_BN_STATS", "WSIS_FUSE_BN_BWD", "WSIS_FWD2", "WSIS_FUSE_BN_FIN", "WSIS_FUSE_BN_APPLY",
+            "WSIS_FUSE_BN_FIN_LVL")
+
+# name -> (kind, arguments, environment, needs the EXPERIMENTAL build)
+CASES = {}
+for _mode in ("train", "eval"):
+    for _dx in (False, True):
+        CASES["%s_dx%d" % (_mode, _dx)] = ("fp32", dict(train=_mode == "train", need_dx=_dx), {}, False)
+_T = dict(train=True, need_dx=True)
+CASES["train_no_fused_stats"] = ("fp32", _T, {"WSIS_FUSE_BN_STATS": "0"}, False)
+CASES["train_no_fused_bn_bwd"] = ("fp32", _T, {"WSIS_FUSE_BN_BWD": "0"}, False)
+CASES["train_no_fwd2"] = ("fp32", _T, {"WSIS_FWD2": "0"}, False)
+CASES["train_bn_sync"] = ("fp32", dict(_T, bn_sync=True), {}, False)
+for _dt in ("bf16", "fp16"):
+    for _f32 in (False, True):
+        CASES["lp_%s_f32out%d" % (_dt, _f32)] = ("lp", dict(dtype=_dt, out_f32=_f32), {}, False)
+CASES["train_stat_fin"] = ("fp32", _T, {"WSIS_FUSE_BN_FIN": "1"}, True)
+CASES["train_bn_in"] = ("fp32", _T, {"WSIS_FUSE_BN_APPLY": "0"}, True)
+CASES["train_bn_in_lvl3_stat_fin_lvl3"] = ("fp32", _T, {"WSIS_FUSE_BN_APPLY": "3", "WSIS_FUSE_BN_FIN": "1",
+                                                     "WSIS_FUSE_BN_FIN_LVL": "3"}, True)
+
+
+def build_model():
+    """one default-config model on the CPU (seeded by harness.build_model)"""
+    import harness
+    torch.manual_seed(0)
+    model, _, _ = harness.build_model(harness.default_cfg(), "cpu")
+    return model
+
+
+@contextlib.contextmanager
+def _environment(env):
+    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k in SWITCHES:
+            os.environ.pop(k, None)
+            if saved[k] is not None:
+                os.environ[k] = saved[k]
+
+
+def _named_tensors(model):
+    named = dict(model.named_parameters())
+    named.update(dict(model.named_buffers()))
+    ts = [named[k] for k in sorted(named)]
+    start = np.array([t.data_ptr() for t in ts], dtype=np.uint64)
+    end = start + np.array([t.numel() * t.element_size() for t in ts], dtype=np.uint64)
+    keep = np.nonzero(end > start)[0]
+    order = keep[np.argsort(start[keep], kind="stable")]
+    start, end = start[order], end[order]
+    assert np.all(end[:-1] <= start[1:]), "parameters and buffers of the model overlap"
+    assert np.all((end <= np.uint64(FAKE_LO)) | (start >= np.uint64(FAKE_HI))), "a host tensor inside the fake range"
+    return start, end, order.astype(np.uint64)
+
+
+def _rewrite(ops, tensors):
+    """plain host pointers of ``ops`` (parameters, BatchNorm buffers) -> PARAM_TAG | index << 32 | byte offset"""
+    start, end, index = tensors
+    for field in ("inp", "out"):
+        p = ops[field].reshape(-1).copy()
+        plain = np.nonzero((p != 0) & ((p < np.uint64(FAKE_LO)) | (p >= np.uint64(FAKE_HI))))[0]
+        j = np.searchsorted(start, p[plain], side="right").astype(np.int64) - 1
+        assert np.all(j >= 0) and np.all(p[plain] < end[np.maximum(j, 0)]), \
+            "an op carries a pointer that is neither symbolic nor inside a parameter or buffer of the model"
+        p[plain] = np.uint64(PARAM_TAG) | (index[j] << np.uint64(32)) | (p[plain] - start[j])
+        ops[field] = p.reshape(ops[field].shape)
+    return ops
+
+
+def _luts(un, c, Mvec, out):
+    """fake look-up tables (one range per tag) from the program's arena layouts, which are recorded on the way"""
+    luts = {}
+    for tag, shift, name in ((un._FWD, 40, "fwd"), (un._BWD, 41, "bwd"), (un._PAR, 42, "par")):
+        arena = getattr(c, name + "_arena", None)
+        offs, total = arena.layout(Mvec) if arena is not None else (np.zeros(0, dtype=np.int64), 0)
+        assert total < (1 << 40)
+        out[name + "_offs"], out[name + "_total"] = np.asarray(offs, dtype=np.int64), np.array([total], dtype=np.int64)
+        luts[tag] = np.asarray(offs).astype(np.uint64) + np.uint64(1 << shift)
+    luts[un._TBL] = np.arange(1, 31, dtype=np.uint64) * np.uint64(4096) + np.uint64(1 << 43)
+    luts[un._EXT] = np.array([0, 1 << 30], dtype=np.uint64) + np.uint64((1 << 43) + (1 << 42))
+    return luts
+
+
+def _acc(entries):
+    """(name code, table handle, level, Cin, Cout) per entry, flattened"""
+    return np.array([[ACC_NAMES[e[0]]] + [int(v) for v in e[1:]] for e in entries], dtype=np.uint64).reshape(-1)
+
+
+def record(model, name):
+    """the arrays of case ``name`` for ``model`` (its training flag is set as the case asks)"""
+    import unet_native as un
+    kind, args, env, _ = CASES[name]
+    Mvec = np.asarray(MVEC, dtype=np.int64)
+    out = {}
+    with _environment(env):
+        model.train(bool(args.get("train", False)))
+        prog = un.UNetProgram(model)
+        if kind == "lp":
+            dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args["dtype"]]
+            c = prog.compiled_lp(dtype, args["out_f32"])
+        else:
+            if args.get("bn_sync"):
+                prog.bn_sync = object()          # compile only: any non-None object selects the synced recording
+            c = prog.compiled(args["need_dx"])
+        luts = _luts(un, c, Mvec, out)
+        tensors = _named_tensors(model)
+        for side in ("fwd", "bwd"):
+            t = getattr(c, side, None)
+            ops = _rewrite(t.instantiate(Mvec, luts), tensors) if t is not None else np.zeros(0, dtype=un.OP_DTYPE)
+            assert ops.dtype == un.OP_DTYPE
+            out[side] = np.frombuffer(ops.tobytes(), dtype=np.uint8)
+    out["ids"] = np.array([getattr(c, "out_id", -1), getattr(c, "dx_id", -1), c.out_channels], dtype=np.int64)
+    out["grad_ids"] = np.asarray(getattr(c, "grad_ids", []), dtype=np.int64)
+    out["grads_done"] = np.asarray(getattr(c, "bwd_grads_done", []), dtype=np.int64)
+    out["acc_f"], out["acc_b"] = _acc(getattr(c, "acc_f", [])), _acc(getattr(c, "acc_b", []))
+    bns = [id(b) for b in prog.bns]
+    out["count"] = np.array([bns.index(id(b)) for b in getattr(c, "count", [])], dtype=np.int64)
+    return out
+
+
+def load():
+    """the fixture as {case: {key: array}}.  The file keeps, per key, the cases' (one-dimensional) arrays joined in the
+    order of ``cases`` and their lengths in ``<key>_len``: the cases differ in little, so they compress as one"""
+    with np.load(FIXTURE) as z:
+        names = [str(n) for n in z["cases"]]
+        out = {n: {} for n in names}
+        for key in z.files:
+            if key == "cases" or key.endswith("_len"):
+                continue
+            ends = np.cumsum(z[key + "_len"])
+            for n, e, l in zip(names, ends, z[key + "_len"]):
+                out[n][key] = z[key][e - l:e]
+    return out
+
+
+def main():
+    sys.path.insert(0, ROOT)
+    importlib.import_module("3d-wsis_amd")
+    import unet_native as un
+    import wsis_native
+    assert wsis_native.experimental(), "the fixture holds all cases: generate it with the EXPERIMENTAL build"
+    model = build_model()
+    recorded = {name: record(model, name) for name in CASES}
+    for name, r in recorded.items():
+        print("%-32s fwd %3d ops, bwd %3d ops" % (name, len(r["fwd"]) // un.OP_DTYPE.itemsize,
+                                                  len(r["bwd"]) // un.OP_DTYPE.itemsize))
+    arrays = {"cases": np.array(list(CASES))}
+    for key in recorded["train_dx1"]:
+        parts = [recorded[name][key] for name in CASES]
+        assert all(p.ndim == 1 for p in parts)
+        arrays[key] = np.concatenate(parts)
+        arrays[key + "_len"] = np.array([len(p) for p in parts], dtype=np.int64)
+    np.savez_compressed(FIXTURE, **arrays)
+    print("unet_program_golden.npz: %d cases, %d bytes" % (len(CASES), os.path.getsize(FIXTURE)))
+
+
+if __name__ == "__main__":
+    main()
