@@ -31,7 +31,12 @@ class PlainGraph(object):
         self.vs = {k: np.asarray(a) for k, a in vs.items()}
         self.edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
         n_e = self.edges.shape[0]
-        self.f = np.zeros((n_e, 13), np.float32) if f is None else np.asarray(f, dtype=np.float32).reshape(n_e, -1)
+        if f is None:
+            self.f = np.zeros((n_e, 13), np.float32)
+        else:
+            f = np.asarray(f, dtype=np.float32)
+            # (a graph without edges: reshape cannot infer the width of an empty array)
+            self.f = f.reshape(n_e, -1) if n_e else f.reshape(0, f.shape[-1] if f.ndim == 2 else 13)
         self.is1ins = np.zeros(n_e, np.int64) if is1ins is None else np.asarray(is1ins, dtype=np.int64)
 
     @property

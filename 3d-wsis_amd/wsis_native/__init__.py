@@ -154,6 +154,15 @@ _HIP_SIGS = {
     "wsis_plane_score_workspace_bytes": (I64, [I64, I32]),
     "wsis_plane_score": (I32, [P, I64, P, I32, F64, P, P, P, I64, P]),
     "wsis_plane_mark": (I32, [P, I64, P, F64, P, P]),
+    "wsis_wl_sp_stats": (I32, [P, P, P, I64, I64, P, P, P, P]),
+    "wsis_wl_neighbor_source": (I32, [P, I64, P, P, P, P, F64, I64, P, P]),
+    "wsis_wl_apply_source": (I32, [P, P, P, P, P, P, I64, I64, P, P, P, P, P]),
+    "wsis_wl_scene_assign": (I32, [P, I64, P, P, P, P, P, P, P, P, F64, I64, P, P, P, P, P, P]),
+    "wsis_wl_point_labels": (I32, [P, I64, P, P, P, P, P]),
+    "wsis_wl_occupancy_workspace_bytes": (I64, [I64]),
+    "wsis_wl_occupancy": (I32, [P, P, P, I64, I32, F32, P, P, I64, P]),
+    "wsis_wl_instance_size": (I32, [P, P, I64, I32, P, P, P]),
+    "wsis_wl_label_stats": (I32, [P, P, P, P, I64, P, I32, P, P]),
     "wsis_semantic_loss_workspace_bytes": (I64, [I64]),
     "wsis_semantic_loss_fwd": (I32, [P, P, I64, I32, I64, P, P, P, I64, P]),
     "wsis_semantic_loss_bwd": (I32, [P, P, I64, I32, I64, P, P, P, P]),

@@ -675,6 +675,66 @@ int wsis_plane_score(const float* d_xyz, int64_t N, const double* d_planes, int3
  * ones equals that call's count. */
 int wsis_plane_mark(const float* d_xyz, int64_t N, const double* d_plane4, double thr, uint8_t* d_mask, void* stream);
 
+/* ---- weak-label stage updates: modules/datasets/scannetv2_dataset.py:515-964 (s3dis_dataset.py has the same methods),
+ * called at the stage boundaries of train_scannetv2.py:477-480, 575-577, 664-666.  The reference builds one mask
+ * `superpoint == spID` per superpoint (O(S*N)); here every per-point stage is one pass.  Labels are int64 [S] with -100
+ * for "none"; a superpoint is LABELLED when semantic and instance label are both != -100; offset vectors are fp64 [S,3].
+ * No floating-point atomics: every float result is bit-identical from run to run.
+ *
+ * wsis_wl_sp_stats replaces every `xyz_origin[superpoint == spID].mean(0)` / `.sum(0)` / `spMask.sum()` of :753-757,
+ * :798-803, :888-889, :909-910, :937-945: d_sum fp32 [S,3], d_count int32 [S], d_centre fp32 [S,3] = sum / count of the
+ * fp32 coordinates, accumulated in fp32 (one wave per superpoint over the CSR d_perm / d_offsets of wsis_segment_csr, fixed
+ * order).  A superpoint without points gets a NaN centre; callers refuse such input. */
+int wsis_wl_sp_stats(const float* d_xyz, const int32_t* d_perm, const int32_t* d_offsets, int64_t N, int64_t S,
+                     float* d_sum, int32_t* d_count, float* d_centre, void* stream);
+/* extend_label_to_neighbor :780-805 / propagate_label_to_neighbor :823-852, the choice of the source: d_src int32 [S] =
+ * the LARGEST labelled k adjacent to n in either direction of d_edges int64 [E,2] with sem[k] == d_pred[n], for n with both
+ * labels -100 and (d_conf != NULL) float64(d_conf[n]) > thr; -1 where there is none.  The reference visits k ascending
+ * and the last writer wins.  d_conf == NULL drops the confidence test (:839).  E == 0 writes -1 everywhere. */
+int wsis_wl_neighbor_source(const int64_t* d_edges, int64_t E, const int64_t* d_sem, const int64_t* d_ins,
+                            const int64_t* d_pred, const float* d_conf, double thr, int64_t S, int32_t* d_src,
+                            void* stream);
+/* What both stages and weak_label_propagation :746-770 write: for every i with k = d_src[i] in [0, S):
+ * sem_out[i] = sem[k], ins_out[i] = ins[k], off_out[i] = (float64(centre[k]) + off[k]) - float64(centre[i]); every other
+ * row is copied.  d_is1ins int64 [E] is recomputed from ins_out for every edge: 0 if either end is -100, -1 if equal,
+ * 1 otherwise (:761-770, :807-816, :854-863).  The outputs may not alias the inputs (the reference reads the old graph). */
+int wsis_wl_apply_source(const int32_t* d_src, const int64_t* d_sem, const int64_t* d_ins, const double* d_off,
+                         const float* d_centre, const int64_t* d_edges, int64_t E, int64_t S, int64_t* d_sem_out,
+                         int64_t* d_ins_out, double* d_off_out, int64_t* d_is1ins, void* stream);
+/* propagate_label_to_whole_scene :873-964.  d_prior int32 [P]: the labelled superpoints, ascending; prior p has the
+ * instance centre c_p = float64(centre[p]) + off[p].  Every superpoint i that is not labelled looks, among the priors
+ * with sem == d_pred[i], for the smallest ||c_p - q_i||_2 (fp64, sqrt((dx*dx + dy*dy) + dz*dz) uncontracted; q_i =
+ * centre[i] + d_pred_off[i] added in fp32; first index on equal distances; priors staged in LDS 256 at a time).
+ * d_assigned int32 [S] = that prior's index in d_prior, or -1 (labelled, no candidate, or distance > max_dist, strict);
+ * d_dist fp64 [S] = the smallest distance (+inf without a candidate).  An assigned i gets the prior's labels and
+ * off_out[i] = g_p - float64(centre[i]) with g_p = sum float64(d_sum[i]) / sum d_count[i] over the superpoints assigned
+ * to p, added in ascending i; every other row is copied.  P == 0 is valid.  The outputs may not alias the inputs. */
+int wsis_wl_scene_assign(const int32_t* d_prior, int64_t P, const int64_t* d_sem, const int64_t* d_ins,
+                         const double* d_off, const float* d_centre, const float* d_sum, const int32_t* d_count,
+                         const int64_t* d_pred, const float* d_pred_off, double max_dist, int64_t S, int32_t* d_assigned,
+                         double* d_dist, int64_t* d_sem_out, int64_t* d_ins_out, double* d_off_out, void* stream);
+/* generate_point_level_weak_label :581-590: fp64 [N] point labels = the two labels of the point's superpoint (d_sp
+ * int64 [N]) if it is labelled, else -100. */
+int wsis_wl_point_labels(const int64_t* d_sp, int64_t N, const int64_t* d_sem, const int64_t* d_ins, double* d_weak_sem,
+                         double* d_weak_ins, void* stream);
+/* cal_occupancy :515-542.  d_rank_sp int32 [S] = rank in [0, R) of the weak instance label the points of a superpoint
+ * carry (-100 has a rank of its own).  d_vox_count int64 [R] = number of distinct (trunc(float32(xyz) * scale)) triples
+ * among the points of each rank: one key pass, wsis_voxelize_idx_map on (rank, voxel), one counting pass. */
+int64_t wsis_wl_occupancy_workspace_bytes(int64_t N);
+int wsis_wl_occupancy(const float* d_xyz, const int64_t* d_sp, const int32_t* d_rank_sp, int64_t N, int32_t R,
+                      float scale, int64_t* d_vox_count, void* d_ws, int64_t ws_bytes, void* stream);
+/* cal_instance_size :545-564.  d_rank int32 [S] = rank in [0, R) of int(instance_label) of every vertex; d_rmax fp64 [R]
+ * = max(0, max ||off_v||_2) over the vertices of the rank (fp64); d_size fp64 [S] = d_rmax[rank].  The maximum is an
+ * integer atomic on the bit pattern of the non-negative norm: independent of the order of arrival. */
+int wsis_wl_instance_size(const double* d_off, const int32_t* d_rank, int64_t S, int32_t R, double* d_rmax,
+                          double* d_size, void* stream);
+/* the label statistics of :602-640 in one pass: d_counters int64 [8] = GT_all, GT_label, semantic_label_num,
+ * correct_semantic_label_num, floor_wall_sem_num, floor_wall_correct_sem_num, instance_label_num,
+ * correct_instance_label_num; h_stuff: HOST array of the n_stuff <= 8 "floor & wall" classes (ScanNet and S3DIS: 0, 1). */
+int wsis_wl_label_stats(const double* d_weak_sem, const double* d_weak_ins, const double* d_sem_gt,
+                        const double* d_ins_gt, int64_t N, const double* h_stuff, int32_t n_stuff, int64_t* d_counters,
+                        void* stream);
+
 /* ---- a18 (point-level part): semantic loss of MultiTaskLoss.forward (losses_3D_WSIS.py:52-67 of the reference):
  * CrossEntropyLoss(ignore_index) + mean_c(1 - dice_c) with dice_c = (2 sum p_c y_c + 1e-5) / (sum p_c^2 + sum y_c
  * + 1e-4 + 1e-5) over the rows whose label != ignore_label, p = softmax(scores).  d_scores fp32 [N,C] (C <= 32),
