@@ -239,7 +239,7 @@ def get_room_walls(xyz, wall_ind, distance=0.1, init_n=3, iter=200, max_num=4, d
 def clustering_in_graph(scene_name, xyz_origin, superpoint, graph, sp_semnatic_pred, pred_sp_offset_vectors,
                         pred_sp_occupancy, pred_sp_ins_size, device="cuda", semantic_ind2label=SEMANTIC_IND2LABEL,
                         valid_labels=INSTANCE_VALID_LABELS, radius_factor=0.25, stuff_classes=(), wall_class=None,
-                        wall_kwargs=None):
+                        wall_kwargs=None, as_tensor=False):
     """``radius_factor``: 0.25 (ScanNet, test_scannetv2.py:331) / 0.8 (S3DIS, test_s3dis.py:349).
     ``stuff_classes``: predicted classes reported as ONE instance each (confidence 1) when they cover more than 100
     points -- ceiling and floor of test_s3dis.py:524-531, appended after the grouped instances.
@@ -247,7 +247,10 @@ def clustering_in_graph(scene_name, xyz_origin, superpoint, graph, sp_semnatic_p
     (open3d's RANSAC ``segment_plane`` in the reference, utils/planeSegment.py); every wall is appended after the stuff
     entries with confidence 1 and label ``semantic_ind2label[wall_class]``, in round order (test_s3dis.py:533-538).
     ``wall_kwargs``: keyword arguments for ``get_room_walls`` (default ``max_num=10``, as test_s3dis.py:533).  With the
-    default ``wall_class=None`` there is no wall split and the call is what it was without the keyword."""
+    default ``wall_class=None`` there is no wall split and the call is what it was without the keyword.
+    ``as_tensor``: return ``ins_mask`` as the int64 [n, N] device tensor it is built as instead of copying it to the host
+    (``wsis_eval`` takes it as it is); without instances it is an empty [0, N] tensor.  ``conf`` and ``label_id`` stay
+    host arrays."""
     assert len(xyz_origin) == len(superpoint)
     N, S = len(xyz_origin), len(sp_semnatic_pred)
     dev = torch.device(device)
@@ -274,7 +277,7 @@ def clustering_in_graph(scene_name, xyz_origin, superpoint, graph, sp_semnatic_p
     seed_size = size[:, 0] if radius_factor == 0.25 else (size[:, 0] * np.float32(radius_factor / 0.25))
     group, n_groups = graph_bfs(label, class_valid, inst_centre, seed_size, adj_off, adj)
     if n_groups == 0 and not stuff_classes and wall_class is None:
-        return np.array([]), np.array([]), np.array([])
+        return np.array([]), np.array([]), (torch.zeros((0, N), dtype=torch.int64, device=dev) if as_tensor else np.array([]))
 
     # points -> group id; voxels per group with ONE voxelization_idx over (group, trunc(xyz * 50))
     group_d = torch.from_numpy(group).to(dev)
@@ -366,8 +369,9 @@ def clustering_in_graph(scene_name, xyz_origin, superpoint, graph, sp_semnatic_p
             label_id.append(semantic_ind2label[int(wall_class)])
             mask_rows.append(w.to(torch.int64).unsqueeze(0))
     if not mask_rows:
-        return np.array([]), np.array([]), np.array([])
-    return np.array(conf), np.array(label_id), torch.cat(mask_rows, 0).cpu().numpy()
+        return np.array([]), np.array([]), (torch.zeros((0, N), dtype=torch.int64, device=dev) if as_tensor else np.array([]))
+    ins_mask = torch.cat(mask_rows, 0)
+    return np.array(conf), np.array(label_id), (ins_mask if as_tensor else ins_mask.cpu().numpy())
 
 
 def superpoint_majority_label(point_pred, superpoint, n_class, device="cuda"):

@@ -163,6 +163,11 @@ _HIP_SIGS = {
     "wsis_wl_occupancy": (I32, [P, P, P, I64, I32, F32, P, P, I64, P]),
     "wsis_wl_instance_size": (I32, [P, P, I64, I32, P, P, P]),
     "wsis_wl_label_stats": (I32, [P, P, P, P, I64, P, I32, P, P]),
+    "wsis_mask_overlap_chunk": (I32, []),
+    "wsis_mask_overlap_tile_rows": (I32, [I32]),
+    "wsis_mask_overlap_workspace_bytes": (I64, [I64, I64, I32]),
+    "wsis_mask_overlap": (I32, [P, I32, I64, I64, P, I32, P, P, P, I64, P]),
+    "wsis_label_pairs": (I32, [P, P, I64, I32, I32, P, P]),
     "wsis_semantic_loss_workspace_bytes": (I64, [I64]),
     "wsis_semantic_loss_fwd": (I32, [P, P, I64, I32, I64, P, P, P, I64, P]),
     "wsis_semantic_loss_bwd": (I32, [P, P, I64, I32, I64, P, P, P, P]),

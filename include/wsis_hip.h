@@ -735,6 +735,31 @@ int wsis_wl_label_stats(const double* d_weak_sem, const double* d_weak_ins, cons
                         const double* d_ins_gt, int64_t N, const double* h_stuff, int32_t n_stuff, int64_t* d_counters,
                         void* stream);
 
+/* ---- evaluation counts: what evaluation/basic/ins_seg_evaluator.py:70-115 (assign_instances_for_scan),
+ * evaluation/basic/instances.py:53-85 (VertInstance.get_instances), utils/eval_s3dis.py:42-112 and
+ * evaluation/basic/sem_seg_evaluator.py:34-37 (fill_confusion) count per scene, called from test_scannetv2.py:133-143,
+ * 212-275, test_s3dis.py:135-148, 216-292 and do_validation (train_scannetv2.py:296-400).  The reference forms one
+ * `np.logical_and(gt_ids == id, pred_mask)` per (prediction, ground-truth instance); here the masks are read once.
+ * Integer counting only: exact, independent of the order of arrival, no floating point.
+ *
+ * wsis_mask_overlap: d_mask row-major [P, N] of elem_bytes = 1 (bool / uint8) or 8 (int64) per element; an element is a
+ * member iff ANY of its bits is set (np.not_equal(mask, 0)).  d_col int32 [N] in [0, G), anything else (negative): the
+ * point counts in d_rows only.  d_table int64 [P, G]: T[p, u] = #{i : mask[p, i] != 0 and col[i] == u}; d_rows int64 [P]
+ * = #{i : mask[p, i] != 0} (instance_count).  Both are zeroed by the call.  P, N >= 0, 1 <= G <= 4096; P == 0 or N == 0
+ * writes zeros without a launch.  A workgroup owns wsis_mask_overlap_chunk() points and wsis_mask_overlap_tile_rows(G)
+ * rows (-1 for G outside the domain), whose counters sit in LDS.  The workspace query returns -1 outside the domain and 0
+ * inside it: this form needs no workspace, d_ws may be NULL. */
+int32_t wsis_mask_overlap_chunk(void);
+int32_t wsis_mask_overlap_tile_rows(int32_t G);
+int64_t wsis_mask_overlap_workspace_bytes(int64_t P, int64_t N, int32_t G);
+int wsis_mask_overlap(const void* d_mask, int32_t elem_bytes, int64_t P, int64_t N, const int32_t* d_col, int32_t G,
+                      int64_t* d_table, int64_t* d_rows, void* d_ws, int64_t ws_bytes, void* stream);
+/* np.add.at(table, (a, b), 1) of sem_seg_evaluator.py:37, and the (instance, class) histogram behind
+ * stats.mode(sem_gt[ins_gt == id]) of utils/eval_s3dis.py:43-46: d_table int64 [A, B], zeroed by the call, counts (a_i, b_i)
+ * for every i with 0 <= a_i < A and 0 <= b_i < B; other points are skipped.  A, B >= 1, A * B <= 65536. */
+int wsis_label_pairs(const int32_t* d_a, const int32_t* d_b, int64_t N, int32_t A, int32_t B, int64_t* d_table,
+                     void* stream);
+
 /* ---- a18 (point-level part): semantic loss of MultiTaskLoss.forward (losses_3D_WSIS.py:52-67 of the reference):
  * CrossEntropyLoss(ignore_index) + mean_c(1 - dice_c) with dice_c = (2 sum p_c y_c + 1e-5) / (sum p_c^2 + sum y_c
  * + 1e-4 + 1e-5) over the rows whose label != ignore_label, p = softmax(scores).  d_scores fp32 [N,C] (C <= 32),
