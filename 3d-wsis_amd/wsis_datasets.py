@@ -3,7 +3,9 @@
 Mirrors ``modules/datasets/scannetv2_dataset.py`` -- ``__getitem__`` (:96-190), ``data_aug_with_graph`` (:194-209),
 ``elastic`` (:225-250), ``crop`` (:252-273), ``get_instance_info`` (:275-309), ``get_cropped_inst_label`` (:311-330)
 and ``collate_fn`` (:343-474, schema in SURVEY App. C) -- on plain numpy arrays.  Pure host code, safe in DataLoader
-workers (``pointgroup_ops.voxelization_idx`` runs in ``libwsis_host.so``).
+workers (``pointgroup_ops.voxelization_idx`` runs in ``libwsis_host.so``).  The last part of the file is the same
+preparation on the device (``DeviceScenePrep``, ``collate_prepared``: csrc/sceneprep.hip) for scenes
+that stay resident in device memory; it is the only part that touches the GPU.
 
 Two deliberate differences:
 
@@ -493,3 +495,369 @@ def acquire_weak_label(xyz, semantic_labels, instance_labels, superpoint, graph,
     off[~keep] = 0.0
     graph.vs["superpoint_offset_vector"] = off
     return [int(c) for c in chosen_all]
+
+
+# ---- the same per-scene preparation on the device ------------------------------------------------------------------
+_SP_STATE_WORDS, _SP_ROUNDS, _SP_ROUND0, SP_MAX_IDS = 144, 32, 16, 65536      # include/wsis_hip.h: the state block
+
+
+def _ordered_to_double(keys):
+    """doubles behind the ordered uint64 keys of the state block (include/wsis_hip.h): key = ~bits for a negative
+    value, bits | 2^63 otherwise"""
+    u = np.ascontiguousarray(keys).view(np.uint64)
+    top = np.uint64(1) << np.uint64(63)
+    return np.where(u & top, u ^ top, ~u).astype(np.uint64).view(np.float64)
+
+
+def _cuda_device(device, what):
+    from wsis_native import WsisError
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise WsisError(f"{what} runs on the MI355X (there is no CPU fallback)")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _as_device(a, dtype, dev, shape=None):
+    if torch.is_tensor(a):
+        t = a.detach().to(device=dev, dtype=dtype)
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(a)).astype(_NP_OF[dtype], copy=False)).to(dev)
+    return (t.reshape(shape) if shape is not None else t).contiguous()
+
+
+_NP_OF = {torch.float32: np.float32, torch.float64: np.float64, torch.int64: np.int64}
+
+
+class ResidentScene(object):
+    """One scene in device memory, uploaded once and prepared every epoch: the per-point arrays of the reference's
+    ``.pth`` 6-tuple (``xyz`` fp32 [N,3], ``rgb`` fp32 [N,3], ``sem`` / ``ins`` / ``sp`` int64 [N]) and the arrays of
+    its superpoint graph (every vertex attribute in its own dtype, ``edges`` int64 [E,2], ``f`` fp32 [E,13], ``is1ins``
+    int64 [E]).  ``logvox``: ``torch.log`` of ``instance_voxel_num`` as the HOST takes it (``collate_fn`` :438) -- the
+    device's log differs in the last bit, and a gather commutes with it.  ``n_ids``: size of the instance-id table."""
+
+    def __init__(self, scene, device):
+        self.scene, self.device = scene, device
+
+    def _set_point_labels(self, semantic_label, instance_label):
+        from wsis_native import WsisError
+        self.sem = _as_device(semantic_label, torch.int64, self.device, (-1,))
+        self.ins = _as_device(instance_label, torch.int64, self.device, (-1,))
+        if self.sem.numel() != self.N or self.ins.numel() != self.N:
+            raise ValueError(f"{self.N} points but {self.sem.numel()} / {self.ins.numel()} labels")
+        self.n_ids = max(int(self.ins.max()) + 1, 0) if self.N else 0          # (at upload time, not per item)
+        if self.n_ids > SP_MAX_IDS:
+            raise WsisError(f"instance id {self.n_ids - 1}: the device re-compaction takes ids below {SP_MAX_IDS}")
+
+    def _set_graph(self, graph):
+        if graph.vcount != self.S:
+            raise ValueError(f"the graph has {graph.vcount} vertices, the scene {self.S} superpoints")
+        dev = self.device
+        self.vs = {k: torch.from_numpy(np.ascontiguousarray(a)).to(dev) for k, a in graph.vs.items()}
+        self.vs["superpoint_offset_vector"] = _as_device(graph.vs["superpoint_offset_vector"], torch.float64, dev, (-1, 3))
+        self.vs_dtype = {k: np.asarray(a).dtype for k, a in graph.vs.items()}
+        self.logvox = None
+        if "instance_voxel_num" in graph.vs:
+            self.logvox = torch.log(torch.as_tensor(np.asarray(graph.vs["instance_voxel_num"])).to(torch.float32)).to(dev)
+        self.edges = _as_device(graph.edges, torch.int64, dev, (-1, 2))
+        self.f = _as_device(graph.f, torch.float32, dev)
+        self.is1ins = _as_device(graph.is1ins, torch.int64, dev, (-1,))
+        self.E = int(self.edges.shape[0])
+        if self.E and (int(self.edges.min()) < 0 or int(self.edges.max()) >= self.S):
+            raise ValueError("edge endpoint outside the graph")
+
+
+class PreparedScene(object):
+    """What ``DeviceScenePrep.__call__`` returns: the fields of ``ScenePrep``'s 12-tuple as device tensors in the
+    dtypes ``collate_fn`` ends with (``loc`` int64 [n,3], ``loc_float`` fp32, ``feat`` fp32, ``sem`` / ``ins`` / ``sp``
+    int64, ``inst_info`` fp32 [n,9], ``inst_pointnum`` int32), the restricted graph (``vs``, ``edges``, ``f``,
+    ``is1ins``) and the host-side counts a collate lays a batch out with."""
+
+    def to_host(self):
+        """the 12-tuple of ``ScenePrep.__call__`` with a :class:`PlainGraph` -- for the host ``collate_fn`` and for
+        comparison.  The labels are int64 and ``loc_float`` fp32 (what ``collate_fn`` casts them to)."""
+        vs = {k: t.cpu().numpy().astype(self.vs_dtype[k], copy=False) for k, t in self.vs.items()}
+        g = PlainGraph(vs, self.edges.cpu().numpy(), self.f.cpu().numpy(), self.is1ins.cpu().numpy())
+        pointnum = self.inst_pointnum.cpu().tolist()
+        return (self.scene, self.loc.cpu(), self.loc_offset.clone(), self.loc_float.cpu(), self.feat.cpu(),
+                self.sem.cpu(), self.ins.cpu(), self.sp.cpu(), g, self.inst_num, self.inst_info.cpu(), pointnum)
+
+
+class DeviceScenePrep(ScenePrep):
+    """``ScenePrep`` on the device (csrc/sceneprep.hip): same constructor arguments, same two random streams consumed
+    in the same order, the per-point work as one pass per stage on a scene that stays in device memory.
+
+    Read-backs per item: the six bounds; one count per crop round (``crop_version=2``: with the kept-point minimum, and
+    one row of three doubles for the random centre); one final vector of counts.  ``last_stats`` holds the launches
+    of this file's native entry points (the CSR build's own launches not included) and the read-backs of the last call.
+
+    Differences from the host class: instance ids are refused above 65,536; an id outside its table is reported with
+    the final counts (``WsisError``) instead of an ``IndexError`` on the spot; a scene without points is refused;
+    ``crop``'s check that the shifted coordinates are non-negative is not repeated; the labels come back as int64 and
+    ``loc_float`` as fp32, what ``collate_fn`` casts them to.  There is no CPU fallback."""
+
+    def __init__(self, *args, device="cuda", **kw):
+        super().__init__(*args, **kw)
+        self.device = _cuda_device(device, "DeviceScenePrep")
+        self.last_stats = {}
+
+    # -- residency -------------------------------------------------------------------------------------------------
+    def upload(self, scene_tuple, graph):
+        xyz, rgb, semantic_label, instance_label, superpoint, scene = scene_tuple
+        dev = self.device
+        R = ResidentScene(scene, dev)
+        with torch.cuda.device(dev):
+            R.xyz = _as_device(xyz, torch.float32, dev, (-1, 3))
+            R.rgb = _as_device(rgb, torch.float32, dev, (-1, 3))
+            R.N, R.S = int(R.xyz.shape[0]), int(graph.vcount)
+            R.sp = _as_device(superpoint, torch.int64, dev, (-1,))
+            if R.rgb.shape[0] != R.N or R.sp.numel() != R.N:
+                raise ValueError(f"{R.N} points but {R.rgb.shape[0]} colours / {R.sp.numel()} superpoint ids")
+            if R.N and (int(R.sp.min()) < 0 or int(R.sp.max()) >= R.S):
+                raise ValueError("superpoint id outside the graph")
+            R._set_point_labels(semantic_label, instance_label)
+            R._set_graph(graph)
+        return R
+
+    def update_labels(self, resident, semantic_label, instance_label, graph):
+        """new point labels and graph arrays after a weak-label stage; coordinates, colours and superpoint ids stay"""
+        with torch.cuda.device(resident.device):
+            resident._set_point_labels(semantic_label, instance_label)
+            resident._set_graph(graph)
+        return resident
+
+    # -- one item ----------------------------------------------------------------------------------------------------
+    def __call__(self, resident):
+        import ctypes
+        import wsis_native as _n
+        from torch_scatter import SegmentCSR
+        R, dev = resident, resident.device
+        lib = _n.hip()
+        stats = {"launches": 0, "readbacks": 0}
+        d3 = ctypes.c_double * 3
+
+        def host3(v):
+            return d3(*[float(x) for x in v])
+
+        with torch.cuda.device(dev):
+            st = _n.stream_ptr()
+            pick = None
+            if self.subsample_train:                     # s3dis_dataset.py:135-144, before any other draw
+                pick = torch.from_numpy(self.rng.choice(R.N, size=R.N // 4, replace=False).astype(np.int64)).to(dev)
+            n = R.N if pick is None else int(pick.numel())
+            flag = bool(self.aug_flag)
+            m = np.ascontiguousarray(self.aug_matrix(flag, flag, flag), dtype=np.float64)
+            m9 = (ctypes.c_double * 9)(*m.reshape(-1).tolist())
+            state = torch.empty(_SP_STATE_WORDS, dtype=torch.int64, device=dev)
+            _n.check(lib.wsis_sp_state_init(_n.ptr(state), st), "sp_state_init")
+            middle = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            scaled = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            _n.check(lib.wsis_sp_affine(_n.ptr(R.xyz), 0, _n.ptr(pick), R.N, n, m9, float(self.scale), _n.ptr(middle),
+                                        _n.ptr(scaled), _n.ptr(state), st), "sp_affine")
+            off_vec = R.vs["superpoint_offset_vector"]
+            off_rot = torch.empty_like(off_vec)
+            _n.check(lib.wsis_sp_affine(_n.ptr(off_vec), 1, None, R.S, R.S, m9, 1.0, _n.ptr(off_rot), None, None, st),
+                     "sp_affine")
+            stats["launches"] += 3
+            if n == 0:
+                raise ValueError("a scene without points cannot be prepared")
+            bounds = _ordered_to_double(state[:6].cpu().numpy())
+            stats["readbacks"] += 1
+            mn, mx = bounds[:3].copy(), bounds[3:].copy()
+            mask, count, off, rnd = None, n, np.zeros(3), 0
+
+            def crop_round(form, a, b):
+                nonlocal mask, rnd
+                if rnd >= _SP_ROUNDS:
+                    raise _n.WsisError("more crop rounds than the state block holds")
+                if mask is None:
+                    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+                _n.check(lib.wsis_sp_crop_mask(_n.ptr(scaled), n, host3(mn), form, host3(a), host3(b), _n.ptr(mask),
+                                               _n.ptr(state), rnd, st), "sp_crop_mask")
+                w = state[_SP_ROUND0 + 4 * rnd:_SP_ROUND0 + 4 * rnd + 4].cpu().numpy()
+                stats["launches"] += 1
+                stats["readbacks"] += 1
+                rnd += 1
+                return int(w[0]), w[1:]
+
+            if not self.test_mode and self.crop_version == 1:           # crop :252-273
+                full_scale = np.array([self.full_scale[1]] * 3)
+                room_range = (mx - mn) - (mn - mn)
+                while count > self.max_npoint:
+                    off = np.clip(full_scale - room_range + 0.001, None, 0) * self.rng.rand(3)
+                    count, _ = crop_round(1, off, full_scale.astype(np.float64))
+                    full_scale[:2] -= 32
+            elif not self.test_mode:                                    # crop_v2 s3dis_dataset.py:285-319
+                room_max = mx - mn
+                centre = scaled[self.rng.choice(n)].cpu().numpy() - mn
+                stats["readbacks"] += 1
+                half_x = max(room_max[0] - centre[0], centre[0])
+                half_y = max(room_max[1] - centre[1], centre[1])
+                steps = np.arange(0, 1, 0.05)
+
+                def inside(s):
+                    dx, dy = half_x * s, half_y * s
+                    return crop_round(2, centre - [dx, dy, 0], centre + [dx, dy, 0])
+
+                low, high = 0, len(steps) - 1
+                while low < high:
+                    mid = int(math.ceil((low + high) / 2))
+                    if inside(steps[mid])[0] <= self.max_npoint:
+                        low = mid
+                    else:
+                        high = mid - 1
+                count, kmin = inside(steps[high])
+                if count == 0:
+                    raise ValueError("crop_v2 kept no point")
+                off = -_ordered_to_double(kmin)
+            n_out = count
+            jit = None
+            if self.aug_flag:
+                jit = (ctypes.c_float * 3)(*(torch.randn(3, generator=self.gen) * 0.1).tolist())
+            S, K = R.S, R.n_ids
+            P = PreparedScene()
+            P.scene, P.device, P.vs_dtype = R.scene, dev, R.vs_dtype
+            P.loc = torch.empty((n_out, 3), dtype=torch.int64, device=dev)
+            P.loc_float = torch.empty((n_out, 3), dtype=torch.float32, device=dev)
+            P.feat = torch.empty((n_out, 3), dtype=torch.float32, device=dev)
+            P.sem = torch.empty(n_out, dtype=torch.int64, device=dev)
+            middle_kept = torch.empty((n_out, 3), dtype=torch.float64, device=dev)
+            ins_raw = torch.empty(n_out, dtype=torch.int64, device=dev)
+            sp_old = torch.empty(n_out, dtype=torch.int64, device=dev)
+            flags = torch.empty(S + K, dtype=torch.int32, device=dev)
+            ws_bytes = int(lib.wsis_sp_emit_workspace_bytes(n, S, K))
+            if ws_bytes < 0:
+                raise _n.WsisError("sp_emit workspace query failed")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _n.check(lib.wsis_sp_emit(_n.ptr(mask), _n.ptr(pick), R.N, n, n_out, _n.ptr(scaled), _n.ptr(middle), host3(mn),
+                                      host3(off), _n.ptr(R.rgb), jit, _n.ptr(R.sem), _n.ptr(R.ins), _n.ptr(R.sp), S, K,
+                                      _n.ptr(P.loc), _n.ptr(P.loc_float), _n.ptr(middle_kept), _n.ptr(P.feat),
+                                      _n.ptr(P.sem), _n.ptr(ins_raw), _n.ptr(sp_old), _n.ptr(flags), _n.ptr(state),
+                                      _n.ptr(ws), ws_bytes, st), "sp_emit")
+            stats["launches"] += 2 + (mask is not None)
+            sp_new = torch.empty(S, dtype=torch.int32, device=dev)
+            subset = torch.zeros(S, dtype=torch.int64, device=dev)
+            ins_map = torch.empty(K, dtype=torch.int32, device=dev)
+            scratch = torch.empty(2 * K, dtype=torch.int32, device=dev)
+            _n.check(lib.wsis_sp_tables(_n.ptr(flags), S, K, _n.ptr(sp_new), _n.ptr(subset), _n.ptr(ins_map),
+                                        _n.ptr(scratch), _n.ptr(state), st), "sp_tables")
+            P.sp = torch.empty(n_out, dtype=torch.int64, device=dev)
+            P.ins = torch.empty(n_out, dtype=torch.int64, device=dev)
+            seg = torch.empty(n_out, dtype=torch.int64, device=dev)
+            _n.check(lib.wsis_sp_relabel(_n.ptr(sp_old), _n.ptr(ins_raw), n_out, _n.ptr(sp_new), S, _n.ptr(ins_map), K,
+                                         _n.ptr(P.sp), _n.ptr(P.ins), _n.ptr(seg), st), "sp_relabel")
+            csr = SegmentCSR(seg, K + 1)
+            P.inst_info = torch.empty((n_out, 9), dtype=torch.float32, device=dev)
+            pointnum = torch.zeros(K, dtype=torch.int32, device=dev)
+            _n.check(lib.wsis_sp_instance_info(_n.ptr(middle_kept), _n.ptr(csr.perm), _n.ptr(csr.offsets), n_out, K,
+                                               _n.ptr(P.inst_info), _n.ptr(pointnum), st), "sp_instance_info")
+            stats["launches"] += 3
+            # ---- the graph side: a few thousand vertices, ~20 k edges (subgraph(subset) :169, PlainGraph.subgraph)
+            kept_v = sp_new >= 0
+            keep_e = kept_v[R.edges[:, 0]] & kept_v[R.edges[:, 1]] if R.E else torch.zeros(0, dtype=torch.bool, device=dev)
+            e_order = torch.argsort(~keep_e, stable=True)                # the kept edges first, in their order
+            e_new = sp_new.long()[R.edges] if R.E else R.edges
+            sp_ins = R.vs["instance_label"].long() if "instance_label" in R.vs else torch.full((S,), -100, device=dev)
+            neg = torch.full((1,), -100, dtype=torch.int64, device=dev)
+            tail = torch.stack([
+                keep_e.sum(),
+                (P.ins.max() + 1) if n_out else neg[0] + 100,
+                torch.where(keep_e, e_new[:, 0], -1).max() if R.E else neg[0] + 99,
+                torch.where(kept_v, sp_ins, neg).max() if S else neg[0]])
+            counts = torch.cat([state[6:13], tail]).cpu().tolist()      # the one final vector of counts
+            stats["readbacks"] += 1
+            bad, locmax, S1, k_inst, E1 = counts[0], counts[2:5], counts[5], counts[6], counts[7]
+            if bad:
+                raise _n.WsisError(f"{bad} ids outside their tables (superpoint id >= {S}, instance id >= {K})")
+            P.inst_num, P.edge_src_max, P.sp_ins_max = int(counts[8]), int(counts[9]), int(counts[10])
+            P.n, P.S, P.E = n_out, int(S1), int(E1)
+            P.extent = np.asarray(locmax, dtype=np.int64) + 1
+            P.loc_offset = torch.from_numpy(mn.copy()).long()           # trunc toward zero (:177)
+            P.inst_pointnum = pointnum[:max(P.inst_num, 0)]
+            sub = subset[:P.S]
+            P.vs = {k: (off_rot if k == "superpoint_offset_vector" else t)[sub] for k, t in R.vs.items()}
+            P.logvox = R.logvox[sub] if R.logvox is not None else None
+            eo = e_order[:P.E]
+            P.edges, P.f, P.is1ins = e_new[eo], R.f[eo], R.is1ins[eo]
+        self.last_stats = stats
+        return P
+
+
+def collate_prepared(items, mode=4, n_levels=5):
+    """``collate_fn`` (:343-474) over :class:`PreparedScene` items, on the device: returns what
+    ``harness.to_device(collate_fn([...]), device)`` returns, the per-point tensors never leaving the device.  The host
+    thread lays the batch out from the items' counts."""
+    import pointgroup_ops
+    import spconv
+    import wsis_native as _n
+    from graphnet import GraphConvInfo
+    from harness import FULL_SCALE_MIN, build_batch_graphs
+    if not items:
+        raise ValueError("empty batch")
+    dev = items[0].device
+    if torch.device(dev).type != "cuda":
+        raise _n.WsisError("collate_prepared runs on the MI355X (there is no CPU fallback)")
+    cols = {k: [] for k in ("locs", "locs_float", "feats", "sem", "ins", "sps", "info", "pointnum", "sp_sem", "sp_ins",
+                            "sp_off", "sp_vox", "sp_size", "edge_sorted", "feat_sorted", "edges_ext", "is1ins")}
+    batch_offsets, sp_batch_offsets, slots = [0], [0], []
+    sp_bias, total_inst, edge_src_rows = 0, 0, 0
+    extent = np.zeros(3, dtype=np.int64)
+    with torch.cuda.device(dev):
+        for i, it in enumerate(items):
+            this_bias = sp_bias
+            cols["sps"].append(it.sp + this_bias if this_bias else it.sp)
+            sp_bias = this_bias + it.S
+            sp_batch_offsets.append(sp_bias)
+            cols["ins"].append(torch.where(it.ins != -100, it.ins + total_inst, it.ins) if total_inst else it.ins)
+            total_inst += it.inst_num
+            batch_offsets.append(batch_offsets[-1] + it.n)
+            cols["locs"].append(torch.cat([torch.full((it.n, 1), i, dtype=torch.int64, device=it.loc.device), it.loc], 1))
+            cols["locs_float"].append(it.loc_float)
+            cols["feats"].append(it.feat)
+            cols["sem"].append(it.sem)
+            cols["info"].append(it.inst_info)
+            cols["pointnum"].append(it.inst_pointnum)
+            cols["sp_sem"].append(it.vs["semantic_label"].long())
+            cols["sp_ins"].append(it.vs["instance_label"].long())
+            cols["sp_off"].append(it.vs["superpoint_offset_vector"].to(torch.float32))
+            cols["sp_vox"].append(it.logvox)
+            cols["sp_size"].append(it.vs["instance_size"].to(torch.float32))
+            order = torch.argsort(it.edges[:, 1], stable=True)          # ecc/GraphConvInfo.py:54-70 (sorted by target)
+            Eb = it.edges + this_bias if this_bias else it.edges
+            cols["edge_sorted"].append(Eb[order])
+            cols["feat_sorted"].append(it.f[order])
+            cols["edges_ext"].append(Eb)
+            cols["is1ins"].append(it.is1ins)
+            if it.E:
+                edge_src_rows = max(edge_src_rows, it.edge_src_max + this_bias + 1)
+            slots.append(max(it.sp_ins_max + 1, 1) if it.S else 1)
+            extent = np.maximum(extent, it.extent)
+
+        def cat(k):
+            return (cols[k][0] if len(cols[k]) == 1 else torch.cat(cols[k], 0)).contiguous()
+        locs = cat("locs")
+        edges = cat("edges_ext")
+        out = {
+            "locs": locs, "locs_offset": torch.stack([it.loc_offset for it in items]),
+            "locs_float": cat("locs_float"), "feats": cat("feats"), "semantic_labels": cat("sem"),
+            "instance_labels": cat("ins"), "instance_info": cat("info"), "instance_pointnum": cat("pointnum"),
+            "offsets": torch.tensor(batch_offsets, dtype=torch.int), "spatial_shape": np.clip(extent, FULL_SCALE_MIN, None),
+            "superpoint": cat("sps"),
+            "GIs": [GraphConvInfo(cat("edge_sorted").t().contiguous(), cat("feat_sorted").float(), sp_bias)],
+            "sp_batch_offsets": torch.tensor(sp_batch_offsets, dtype=torch.int),
+            "edge_u_list": edges[:, 0].contiguous(), "edge_v_list": edges[:, 1].contiguous(),
+            "edge_src_rows": edge_src_rows, "is1ins_labels": cat("is1ins"),
+            "superpoint_semantic_labels": cat("sp_sem"), "superpoint_instance_labels": cat("sp_ins"),
+            "superpoint_offset_vector": cat("sp_off"), "superpoint_instance_voxel_num": cat("sp_vox"),
+            "superpoint_instance_size": cat("sp_size"), "scene_list": [it.scene for it in items],
+            "sp_instance_slots": slots,
+        }
+        voxel_locs, p2v_map, v2p_map = pointgroup_ops.voxelization_idx(locs, len(items), mode)
+        counts = spconv.ops.level_voxel_counts_device(voxel_locs, out["spatial_shape"], n_levels)
+        out.update(voxel_locs=voxel_locs, p2v_map=p2v_map, v2p_map=v2p_map)
+        out["level_counts"] = [int(c) for c in counts.tolist()]
+        out["voxel_coords_int"] = voxel_locs.int().contiguous()
+        ev = torch.cuda.Event()
+        ev.record()
+        out["coords_ready_event"] = ev
+        build_batch_graphs(out)
+    return out

@@ -163,6 +163,15 @@ _HIP_SIGS = {
     "wsis_wl_occupancy": (I32, [P, P, P, I64, I32, F32, P, P, I64, P]),
     "wsis_wl_instance_size": (I32, [P, P, I64, I32, P, P, P]),
     "wsis_wl_label_stats": (I32, [P, P, P, P, I64, P, I32, P, P]),
+    "wsis_sp_state_bytes": (I64, []),
+    "wsis_sp_state_init": (I32, [P, P]),
+    "wsis_sp_affine": (I32, [P, I32, P, I64, I64, P, F64, P, P, P, P]),
+    "wsis_sp_crop_mask": (I32, [P, I64, P, I32, P, P, P, P, I32, P]),
+    "wsis_sp_emit_workspace_bytes": (I64, [I64, I64, I64]),
+    "wsis_sp_emit": (I32, [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64] + [P] * 9 + [P, I64, P]),
+    "wsis_sp_tables": (I32, [P, I64, I64, P, P, P, P, P, P]),
+    "wsis_sp_relabel": (I32, [P, P, I64, P, I64, P, I64, P, P, P, P]),
+    "wsis_sp_instance_info": (I32, [P, P, P, I64, I64, P, P, P]),
     "wsis_mask_overlap_chunk": (I32, []),
     "wsis_mask_overlap_tile_rows": (I32, [I32]),
     "wsis_mask_overlap_workspace_bytes": (I64, [I64, I64, I32]),

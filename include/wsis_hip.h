@@ -735,6 +735,84 @@ int wsis_wl_label_stats(const double* d_weak_sem, const double* d_weak_ins, cons
                         const double* d_ins_gt, int64_t N, const double* h_stuff, int32_t n_stuff, int64_t* d_counters,
                         void* stream);
 
+/* ---- per-scene preparation of a training item: ScanNetV2Inst_spg.__getitem__ (modules/datasets/scannetv2_dataset.py:96-190)
+ * and its S3DIS twin (s3dis_dataset.py:126-206), one pass per stage over data that stays on the device (csrc/sceneprep.hip;
+ * driven by wsis_datasets.DeviceScenePrep).  No floating-point atomics: every float result is bit-identical from run to
+ * run.  Sizes are below 2^31; instance ids are below WSIS_SP_MAX_IDS (the reference has no such limit: more ids are
+ * refused with WSIS_ERR_OVERFLOW).  Unlike the reference, an id outside its table (a superpoint id >= S, an instance id
+ * >= n_ids, an index of d_pick outside [0, n_src), more ones in a mask than n_out) is not an exception on the spot: it is
+ * counted in word 6 of the state block, which the caller reads with its other counts.
+ *
+ * The state block: WSIS_SP_STATE_WORDS uint64 words in device memory, set up by wsis_sp_state_init once per item.
+ *   words 0-2 / 3-5   per-column minimum / maximum of xyz_scaled, as ORDERED keys of the doubles (key = ~bits for a
+ *                     negative value, bits | 2^63 otherwise: unsigned order of the keys = order of the doubles)
+ *   word 6            number of out-of-table ids met (0 on valid input)
+ *   words 8-10        per-column maximum of loc (wsis_sp_emit)
+ *   word 11, 12       number of kept superpoints S', number of instance ids present k (wsis_sp_tables)
+ *   words 16+4r ..    crop round r < WSIS_SP_ROUNDS: number of ones of its mask, then the ordered keys of the per-column
+ *                     minimum of x over the kept points (all-ones keys when the mask is empty) */
+#define WSIS_SP_ROUNDS 32
+#define WSIS_SP_STATE_WORDS (16 + 4 * WSIS_SP_ROUNDS)
+#define WSIS_SP_MAX_IDS 65536
+int64_t wsis_sp_state_bytes(void);
+int wsis_sp_state_init(void* d_state, void* stream);
+/* data_aug_with_graph :194-209 with the matrix of :211-222 drawn by the caller, `xyz = xyz_middle * scale` :149 and the
+ * bounds behind `xyz -= xyz.min(0)` :151-152 and room_range :259.  d_in [n_src,3] fp32 (in_f64 == 0) or fp64 (the graph's
+ * superpoint_offset_vector); row i of the outputs comes from row d_pick[i] of d_in (d_pick int64 [n], the S3DIS quarter
+ * of s3dis_dataset.py:135-144) or from row i (d_pick NULL).  h_m9: HOST fp64 [3,3] row-major.  d_middle fp64 [n,3], column
+ * j = fma(z, m[2][j], fma(y, m[1][j], x * m[0][j])) on coordinates widened to fp64 -- np.matmul's result bit for bit;
+ * d_scaled fp64 [n,3] = d_middle * scale and the bounds in the state block (both skipped when d_scaled is NULL; d_state
+ * may then be NULL too). */
+int wsis_sp_affine(const void* d_in, int32_t in_f64, const int64_t* d_pick, int64_t n_src, int64_t n, const double* h_m9,
+                   double scale, double* d_middle, double* d_scaled, void* d_state, void* stream);
+/* One round of crop :252-273 (form 1) or of crop_v2 s3dis_dataset.py:285-319 (form 2) on x = d_scaled - h_min3 (HOST
+ * fp64 [3], the decoded minima): form 1, mask_i = all_j(x_ij + a_j >= 0) and all_j(x_ij + a_j < b_j) with a = offset, b =
+ * full_scale; form 2, mask_i = a_j <= x_ij <= b_j on columns 0 and 1 (a = lo, b = hi).  One fp64 operation and one
+ * compare per element, as the reference: the mask is exact.  d_mask uint8 [n]; the count and the kept-point minima go to
+ * round `round` of the state block.  The loops, and with them the order of the random draws, stay with the caller. */
+int wsis_sp_crop_mask(const double* d_scaled, int64_t n, const double* h_min3, int32_t form, const double* h_a3,
+                      const double* h_b3, uint8_t* d_mask, void* d_state, int32_t round, void* stream);
+/* The boolean-mask gathers of :155-160 in the dtypes collate_fn ends with (:343-474), kept points in their original
+ * order (d_mask NULL: every point).  For kept point i, output row o, source row p = d_pick[i] or i:
+ *   d_loc int64 [n_out,3] = trunc toward zero of ((d_scaled[i] - h_min3) + h_off3) (`torch.from_numpy(xyz).long()` :176;
+ *     h_off3 = the last crop offset, or minus the kept-point minimum for crop_v2), its column maxima in the state block;
+ *   d_loc_float fp32 = d_middle[i] rounded to nearest, d_middle_kept fp64 = d_middle[i];
+ *   d_feat fp32 = d_rgb[p] + h_jitter3 (HOST fp32 [3]; NULL: no jitter);  d_sem_out = d_sem[p];
+ *   d_ins_raw = d_ins[p], the instance label before re-compaction;  d_sp_old = d_sp[p].
+ * d_flags int32 [S + n_ids], zeroed by the call: [s] = 1 for every kept superpoint id, [S + id] = 1 for every kept
+ * instance id >= 0.  n_out: rows the outputs have room for (the count of the mask).  The workspace holds one count per
+ * 1024 points; the query returns -1 outside the domain. */
+int64_t wsis_sp_emit_workspace_bytes(int64_t n, int64_t S, int64_t n_ids);
+int wsis_sp_emit(const uint8_t* d_mask, const int64_t* d_pick, int64_t n_src, int64_t n, int64_t n_out,
+                 const double* d_scaled, const double* d_middle, const double* h_min3, const double* h_off3,
+                 const float* d_rgb, const float* h_jitter3, const int64_t* d_sem, const int64_t* d_ins,
+                 const int64_t* d_sp, int64_t S, int64_t n_ids, int64_t* d_loc, float* d_loc_float,
+                 double* d_middle_kept, float* d_feat, int64_t* d_sem_out, int64_t* d_ins_raw, int64_t* d_sp_old,
+                 int32_t* d_flags, void* d_state, void* d_ws, int64_t ws_bytes, void* stream);
+/* The two id tables from d_flags of wsis_sp_emit, one workgroup, O(S + n_ids), no sort:
+ *   np.unique(superpoint, return_inverse=True) :169 -- d_subset int64 [S]: the first S' entries are the kept ids,
+ *     ascending; d_sp_new int32 [S]: the rank of a kept id, -1 otherwise;
+ *   get_cropped_inst_label :311-330 -- d_ins_map int32 [n_ids]: new id of a present id, -1 otherwise.  The reference walks
+ *     j upward while j < the current maximum and lets an empty j take over the points of the current largest id: with k
+ *     ids present, the i-th empty id below k takes the i-th largest present id, ids below k stay.
+ * d_scratch int32 [2 * n_ids].  S' and k go to the state block. */
+int wsis_sp_tables(const int32_t* d_flags, int64_t S, int64_t n_ids, int32_t* d_sp_new, int64_t* d_subset,
+                   int32_t* d_ins_map, int32_t* d_scratch, void* d_state, void* stream);
+/* One gather per point: d_sp_out int64 [n] = d_sp_new[d_sp_old], d_ins_out int64 [n] = d_ins_map[d_ins_raw] with
+ * negative labels (-100) passed through, d_seg int64 [n] = d_ins_out, or n_ids for a point without an instance: the
+ * index vector whose wsis_segment_csr (n_ids + 1 segments) wsis_sp_instance_info walks. */
+int wsis_sp_relabel(const int64_t* d_sp_old, const int64_t* d_ins_raw, int64_t n, const int32_t* d_sp_new, int64_t S,
+                    const int32_t* d_ins_map, int64_t n_ids, int64_t* d_sp_out, int64_t* d_ins_out, int64_t* d_seg,
+                    void* stream);
+/* get_instance_info :275-309.  d_perm / d_offsets: CSR of d_seg over K + 1 segments.  One wave per instance id: fp64 sum
+ * (lane l adds the points l, l + 64, ... of the row in order, then one xor butterfly), minimum and maximum of d_middle
+ * fp64 [n,3]; d_info fp32 [n,9] row of every point of the id = (sum / count, min, max), each cast to fp32; the points of
+ * segment K (no instance) get -100.0 in all nine columns; d_pointnum int32 [K] = points per id.  An id without points
+ * writes no row and count 0 (the reference would fail on its empty minimum).  The order of the sum is fixed but not
+ * numpy's: columns 0:3 may differ from the reference by one fp32 step, never more. */
+int wsis_sp_instance_info(const double* d_middle, const int32_t* d_perm, const int32_t* d_offsets, int64_t n, int64_t K,
+                          float* d_info, int32_t* d_pointnum, void* stream);
+
 /* ---- evaluation counts: what evaluation/basic/ins_seg_evaluator.py:70-115 (assign_instances_for_scan),
  * evaluation/basic/instances.py:53-85 (VertInstance.get_instances), utils/eval_s3dis.py:42-112 and
  * evaluation/basic/sem_seg_evaluator.py:34-37 (fill_confusion) count per scene, called from test_scannetv2.py:133-143,
