@@ -83,7 +83,9 @@ class MultiTaskLoss(nn.Module):
             else:       # dropped rows -> zero rows: every column sum of the dice terms is unchanged
                 w = keep.unsqueeze(1).to(semantic_scores.dtype)
                 semantic_scores = F.softmax(semantic_scores, dim=-1) * w
-                one_hot = F.one_hot(semantic_labels.clamp(min=0), num_classes=self.semantic_class_num) * w
+                # (dropped rows -> class 0: any ignore_label, negative or not, stays inside one_hot's range)
+                one_hot = F.one_hot(torch.where(keep, semantic_labels, torch.zeros_like(semantic_labels)),
+                                    num_classes=self.semantic_class_num) * w
             semantic_loss = semantic_loss + dice_loss_multi_classes(semantic_scores, one_hot).mean()
         if not fused:
             loss_out["semantic_loss"] = (semantic_loss, semantic_scores.sum())
@@ -264,13 +266,13 @@ class MultiTaskLoss(nn.Module):
         dist = torch.norm(pred - mu_rows, p=2, dim=1)
         dist = torch.square(torch.clamp(dist - self.delta_v, min=0.))
         w = oh @ inv                                             # [S] 1 / size of the row's instance, 0 if dropped
-        l_var = torch.sum(dist * w) / n
+        l_var = torch.sum(dist * w) / n.clamp(min=1.0)           # (n >= 1: x / n unchanged; n == 0: see _nan_if_empty)
         l1 = (mu.unsqueeze(0) - mu.unsqueeze(1)).abs().sum(-1)   # [I, I]
         d = 2. * self.delta_d - l1
         pair = present.unsqueeze(0) * present.unsqueeze(1) * (1.0 - torch.eye(n_slots, device=pred.device, dtype=pred.dtype))
         l_dist = torch.sum(torch.square(torch.clamp(d, min=0.)) * pair) / torch.clamp(n * (n - 1), min=1.0)
         l_reg = torch.sum(torch.norm(mu, p=2, dim=1) * present)
-        return self.param_var * l_var + self.param_dist * l_dist + self.param_reg * l_reg
+        return _nan_if_empty(self.param_var * l_var + self.param_dist * l_dist + self.param_reg * l_reg, n)
 
     def discriminative_loss_masked(self, prediction, label, valid):
         """the same pull / push / reg terms (losses_3D_WSIS.py:157-230) without ``unique`` / mask indexing: rows with
@@ -285,7 +287,7 @@ class MultiTaskLoss(nn.Module):
         mu = (same @ pred) / count.unsqueeze(1)                  # [S,D]: the mean of the row's instance
         dist = torch.norm(pred - mu, p=2, dim=1)
         dist = torch.square(torch.clamp(dist - self.delta_v, min=0.))
-        l_var = torch.sum(dist * w) / n
+        l_var = torch.sum(dist * w) / n.clamp(min=1.0)           # (n >= 1: x / n unchanged; n == 0: see _nan_if_empty)
         # L1 distance of every row pair (row pair (i,j) stands for instance pair (c_i,c_j)).  Broadcast form:
         # torch.cdist(p=1) took 0.85 ms forward + 0.52 ms backward for 1190 rows (one thread per pair, 7-term loop)
         l1 = (mu.unsqueeze(0) - mu.unsqueeze(1)).abs().sum(-1)
@@ -294,16 +296,27 @@ class MultiTaskLoss(nn.Module):
         pair_w = other * w.unsqueeze(0) * w.unsqueeze(1)         # every ordered instance pair weighs 1 in total
         l_dist = torch.sum(torch.square(torch.clamp(d, min=0.)) * pair_w) / torch.clamp(n * (n - 1), min=1.0)
         l_reg = torch.sum(torch.norm(mu, p=2, dim=1) * w)
-        return self.param_var * l_var + self.param_dist * l_dist + self.param_reg * l_reg
+        return _nan_if_empty(self.param_var * l_var + self.param_dist * l_dist + self.param_reg * l_reg, n)
+
+
+def _nan_if_empty(value, n):
+    """``value`` for n > 0, NaN for n == 0 -- what the reference's mean over an empty selection gives.  The NaN is
+    SELECTED, not computed: ``value`` is formed with its denominator clamped to 1, so the untaken branch hands a zero
+    gradient (not 0 * inf = NaN) to every input, as boolean indexing does, and the other loss terms of a crop without
+    a labelled superpoint still train.  For n > 0 value and gradient keep their bits."""
+    return torch.where(n > 0, value, torch.full_like(value, float("nan")))
 
 
 def _masked_l1(pred, target, row_valid):
-    """nn.L1Loss()(pred[row_valid], target[row_valid]) without the boolean indexing"""
-    w = row_valid.to(pred.dtype)
+    """nn.L1Loss()(pred[row_valid], target[row_valid]) without the boolean indexing; dropped rows are selected away,
+    not multiplied by 0 (the log voxel count of an unlabelled superpoint is -inf, and inf * 0 is NaN)"""
+    w = row_valid
     while w.dim() < pred.dim():
         w = w.unsqueeze(-1)
     per_row = pred[0].numel() if pred.dim() > 1 else 1
-    return torch.sum(torch.abs(pred - target) * w) / (row_valid.sum() * per_row)
+    diff = torch.abs(pred - target)
+    den = row_valid.sum() * per_row
+    return _nan_if_empty(torch.sum(torch.where(w, diff, torch.zeros_like(diff))) / den.clamp(min=1), den)
 
 
 def dice_loss_multi_classes(input, target, epsilon=1e-5, weight=None):
