@@ -151,21 +151,34 @@ inline SyncSlot* sync_slot(void* d_sync, int i) {
 }
 inline void* deep_sync_slot(void* d_sync) { return d_sync ? static_cast<SyncSlot*>(d_sync) + kSyncSlots : nullptr; }
 
-// mean / biased variance (+ running statistics) of one channel from the fp64 totals of the centred slice partials:
-// S = sum of slice sums, Q = sum of the slices' centred sums of squares, W = sum S_i^2 / n_i (Chan's combination)
-__device__ __forceinline__ void bn_finish_centred(double S, double Q, double W, int64_t M, int c, float* mean, float* var,
-                                                  float* running_mean, float* running_var, float momentum) {
+// mean and biased variance of one channel in fp64, and their write-out: mean, var and, with a running pair, the running
+// statistics (unbiased variance) over n rows.  Every statistics finish of the library stores through bn_store_stats.
+struct BnMeanVar {
+  double mu, v;
+};
+__device__ __forceinline__ void bn_store_stats(BnMeanVar s, int64_t M, int c, float* mean, float* var, float* running_mean,
+                                               float* running_var, float momentum) {
+  const double n = (double)M;
+  mean[c] = (float)s.mu;
+  var[c] = (float)s.v;
+  if (running_mean) {
+    const double unb = n > 1 ? s.v * n / (n - 1) : s.v;
+    running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * s.mu);
+    running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
+  }
+}
+// from the fp64 totals of the centred slice partials: S = sum of slice sums, Q = sum of the slices' centred sums of
+// squares, W = sum S_i^2 / n_i (Chan's combination)
+__device__ __forceinline__ BnMeanVar bn_centred_mean_var(double S, double Q, double W, int64_t M) {
   const double n = (double)M;
   const double mu = S / n;
   double v = (Q + (W - n * mu * mu)) / n;
   if (v < 0.0) v = 0.0;
-  mean[c] = (float)mu;
-  var[c] = (float)v;
-  if (running_mean) {
-    const double unb = n > 1 ? v * n / (n - 1) : v;
-    running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mu);
-    running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unb);
-  }
+  return {mu, v};
+}
+__device__ __forceinline__ void bn_finish_centred(double S, double Q, double W, int64_t M, int c, float* mean, float* var,
+                                                  float* running_mean, float* running_var, float momentum) {
+  bn_store_stats(bn_centred_mean_var(S, Q, W, M), M, c, mean, var, running_mean, running_var, momentum);
 }
 
 // number of chunks / partial rows per chunk of the two-level statistics finish (bn.hip and the in-launch finish of
