@@ -172,6 +172,10 @@ _HIP_SIGS = {
     "wsis_sp_tables": (I32, [P, I64, I64, P, P, P, P, P, P]),
     "wsis_sp_relabel": (I32, [P, P, I64, P, I64, P, I64, P, P, P, P]),
     "wsis_sp_instance_info": (I32, [P, P, P, I64, I64, P, P, P]),
+    "wsis_gp_sp_moments": (I32, [P, P, P, I64, I64, P, P, P, P, P, P, P, P]),
+    "wsis_gp_label_mode": (I32, [P, P, P, I64, I64, P, P, P]),
+    "wsis_gp_neighbors": (I32, [P, I64, I32, F64, P, P, P, P]),
+    "wsis_gp_edge_features": (I32, [P, P, P, I64, I64, P, I64, P, P, P, P, P, P, P, P]),
     "wsis_mask_overlap_chunk": (I32, []),
     "wsis_mask_overlap_tile_rows": (I32, [I32]),
     "wsis_mask_overlap_workspace_bytes": (I64, [I64, I64, I32]),

@@ -813,6 +813,51 @@ int wsis_sp_relabel(const int64_t* d_sp_old, const int64_t* d_ins_raw, int64_t n
 int wsis_sp_instance_info(const double* d_middle, const int32_t* d_perm, const int32_t* d_offsets, int64_t n, int64_t K,
                           float* d_info, int32_t* d_pointnum, void* stream);
 
+/* ---- building the superpoint graph of a scene: data/ScanNetV2/prepare_data_inst_ScanNetV2.py (build_weak_label_graph
+ * :172-285, compute_edges_feature :340-433) and data/S3DIS/prepare_S3DIS_inst_data.py (build_graph_10NBR :101-224,
+ * compute_edges_feature :268-358), the per-point and per-pair parts (csrc/graphprep.hip; driven by wsis_graph_prep).  The
+ * reference forms one `np.where(superpoint == spID)` mask per superpoint and use (O(S*N)); here one wave walks one row of
+ * the point CSR d_perm / d_offsets of wsis_segment_csr (stable: a row lists its points in ascending index order, the
+ * order of xyz[np.where(superpoint == spID)[0]]).  No floating-point atomics, fixed summation order (lane l takes the
+ * entries l, l + 64, ... of its row, then one xor butterfly): two calls give the same bytes.
+ *
+ * wsis_gp_sp_moments replaces the superpoint loop of compute_edges_feature (ScanNet :359-394, S3DIS :287-322) and the
+ * centres of :208-211 / :132-135.  d_count int64 [S]; d_centroid fp32 [S,3] = the fp64 mean of the widened fp32
+ * coordinates, rounded; d_cov6 fp64 [S,6] = (xx, yy, zz, xy, xz, yz) central second moments about that fp64 mean, divided
+ * by n - 1 for n >= 3 (np.cov), by n for n == 2 (np.var), zero for n == 1; d_ev3 fp64 [S,3] = its eigenvalues, descending
+ * (cyclic Jacobi, at most 12 sweeps), zero for n < 3.  d_length / d_surface / d_volume fp32 [S]: n == 1: 0, 0, 0;
+ * n == 2: sqrt(xx + yy + zz), 0, 0; n >= 3: ev0, sqrt(ev0 * ev1 + 1e-10), sqrt(ev0 * ev1 * ev2 + 1e-10), evaluated in fp64
+ * and rounded.  d_cov6 and d_ev3 may be NULL. */
+int wsis_gp_sp_moments(const float* d_xyz, const int32_t* d_perm, const int32_t* d_offsets, int64_t N, int64_t S,
+                       int64_t* d_count, float* d_centroid, float* d_length, float* d_surface, float* d_volume,
+                       double* d_cov6, double* d_ev3, void* stream);
+/* stats.mode(labels[spMask])[0][0] of ScanNet :241-249 / S3DIS :173-183.  d_rank int32 [N]: the dense rank of every
+ * point's label among the distinct label values in ascending order (-100 has a rank like any other value).  d_mode int32
+ * [S] = the most frequent rank of the row, the smallest one on a tie (-1 for a row without points); d_mode_count int32 [S]
+ * = how often it occurs.  Integer only; cost = distinct labels of the row x row length. */
+int wsis_gp_label_mode(const int32_t* d_rank, const int32_t* d_perm, const int32_t* d_offsets, int64_t N, int64_t S,
+                       int32_t* d_mode, int32_t* d_mode_count, void* stream);
+/* KDTree(superpoint_center).query_radius(r) of ScanNet :213-215 / .query(k = 11) of S3DIS :141-156, by brute force over the
+ * d_centres fp32 [S,3]: d2 = (dx*dx + dy*dy) + dz*dz on coordinates widened to fp64, uncontracted.  Row s of d_nbr int32
+ * [S,k] / d_dist2 fp64 [S,k]: the OTHER superpoints (self is excluded by id) with d2 <= radius * radius, ascending in
+ * (d2, id), padded with -1 / +inf; d_count int32 [S] = how many satisfy the radius, which may exceed k.  radius may be
+ * +inf; 1 <= k <= 128. */
+int wsis_gp_neighbors(const float* d_centres, int64_t S, int32_t k, double radius, int32_t* d_nbr, double* d_dist2,
+                      int32_t* d_count, void* stream);
+/* The edge loop of compute_edges_feature (ScanNet :398-426, S3DIS :325-354): d_out fp32 [E,13] = delta mean 3, delta std 3,
+ * centroid[s] - centroid[t] 3, length / surface / volume ratios a[s] / (a[t] + 1e-6f) in fp32, the point-count ratio
+ * n_s / (n_t + 1e-6) in fp64 rounded to fp32, for the directed edges d_edges int64 [E,2].  Pair j of (s, t) = (point j of
+ * the smaller row, point d_samp[d_samp_off[e] + j] of the larger row), (j, j) for rows of equal length: the caller draws
+ * the np.random.choice(n_big, n_small, replace=False) of :409-412 and passes them as one CSR (d_samp_off int64 [E+1],
+ * d_samp int32; an edge between rows of equal length has an empty list).  delta = xs - xt in fp32; its mean and population
+ * standard deviation per column in fp64 (two passes), rounded to fp32; one pair: mean = delta, std = 0 (:419-421).  An
+ * edge with an endpoint outside [0, S) or a list of the wrong length gets a row of NaN; a sample index is clamped to its
+ * row. */
+int wsis_gp_edge_features(const float* d_xyz, const int32_t* d_perm, const int32_t* d_offsets, int64_t N, int64_t S,
+                          const int64_t* d_edges, int64_t E, const int64_t* d_samp_off, const int32_t* d_samp,
+                          const float* d_centroid, const float* d_length, const float* d_surface, const float* d_volume,
+                          float* d_out, void* stream);
+
 /* ---- evaluation counts: what evaluation/basic/ins_seg_evaluator.py:70-115 (assign_instances_for_scan),
  * evaluation/basic/instances.py:53-85 (VertInstance.get_instances), utils/eval_s3dis.py:42-112 and
  * evaluation/basic/sem_seg_evaluator.py:34-37 (fill_confusion) count per scene, called from test_scannetv2.py:133-143,
