@@ -10,6 +10,7 @@ host-known shape (rows that the reference drops get weight 0; per-instance means
 matrix instead of ``unique``), so the host never waits for the GPU inside the loss and can keep issuing the backward
 pass while the forward is still running.  ``WSIS_LOSS_INDEXED=1`` selects the reference-shaped evaluation; both are
 checked against the golden vectors."""
+import functools
 import os
 
 import torch
@@ -20,6 +21,16 @@ import torch.nn.functional as F
 class _NullLogger(object):
     def info(self, *a, **k):
         pass
+
+
+def _ops():
+    """the device operators and their kernels' limits: the one import site, lazy (the host evaluations do without)"""
+    import wsis_ops
+    return wsis_ops
+
+
+def _on(switch, default="1"):
+    return os.environ.get(switch, default) != "0"
 
 
 class MultiTaskLoss(nn.Module):
@@ -50,17 +61,49 @@ class MultiTaskLoss(nn.Module):
 
     def forward(self, loss_inp, epoch):
         loss_out = {}
-        semantic_labels, instance_labels = loss_inp["point_labels"]
-        semantic_scores = loss_inp["semantic_scores"]
         indexed = os.environ.get("WSIS_LOSS_INDEXED", "0") == "1"
-        fused = (not indexed and self.semantic_dice and semantic_scores.is_cuda and semantic_scores.shape[1] <= 32
-                 and os.environ.get("WSIS_FUSE_SEM_LOSS", "1") != "0")
-        if fused:       # CE + dice in two passes over [N, C] (csrc/loss.hip) instead of ~40 torch launches
-            import wsis_ops
+
+        @functools.lru_cache(maxsize=None)
+        def valid():
+            # (mask, count) of the superpoints that both labels keep: only the unfused branches read them (the fused
+            # kernels take the two label tensors), so they are formed on first use -- four launches the default device
+            # path never needs
+            sp_sem_labels, sp_ins_labels = loss_inp["superpoint_labels"]
+            m = (sp_ins_labels != self.ignore_label) & (sp_sem_labels != self.ignore_label)
+            return m, m.sum()
+
+        semantic_loss, side_join = self._point_semantic(loss_inp, indexed, loss_out)
+        terms, paired = [("point semantic loss", semantic_loss)], 0
+        if epoch > self.joint_training_epoch:
+            terms.append(("sp semantic loss", self._sp_semantic(loss_inp, indexed, loss_out)))
+            offset_norm, offset_dir, occupancy, instance_size, n_reg = self._sp_regression(loss_inp, indexed, valid)
+            if self.supervise_sp_offset:
+                loss_out["offset_norm_loss"], loss_out["offset_dir_loss"] = (offset_norm, n_reg), (offset_dir, n_reg)
+                paired |= 1 << len(terms)                  # loss + (offset_norm_loss + offset_dir_loss)
+                terms += [("sp offset norm loss", offset_norm), ("sp offset dir loss", offset_dir)]
+            terms.append(("sp discriminative loss", self._sp_discriminative(loss_inp, indexed, valid, loss_out)))
+            if self.supervise_instance_size:
+                loss_out["occupancy_loss"], loss_out["instance_size_loss"] = (occupancy, n_reg), (instance_size, n_reg)
+                terms += [("sp occupancy loss", occupancy), ("sp instance size loss", instance_size)]
+        if side_join is not None:       # the point term joins the others here
+            main, side, made = side_join
+            main.wait_stream(side)
+            for t in made:
+                t.record_stream(main)
+        return self._sum_terms(terms, paired), loss_out
+
+    def _point_semantic(self, inp, indexed, loss_out):
+        """CrossEntropy(ignore_index) (+ dice) of the point scores -> (term, side-stream join or None)"""
+        semantic_labels, semantic_scores = inp["point_labels"][0], inp["semantic_scores"]
+        if (not indexed and self.semantic_dice and semantic_scores.is_cuda and _on("WSIS_FUSE_SEM_LOSS")
+                and semantic_scores.shape[1] <= _ops().LOSS_MAX_CLASSES):
+            # CE + dice in two passes over [N, C] (csrc/loss.hip) instead of ~40 torch launches
+            wsis_ops = _ops()
             # on the point-level head's branch stream (backbone_3D_WSIS.py): the two passes over [N, C] and their backward
             # run beside the superpoint terms instead of in front of them
             side = wsis_ops.branch_stream(semantic_scores.device, 1)
-            if side is not None and os.environ.get("WSIS_BRANCH_LOSS", "0") != "0":      # (measured: within the noise)
+            join = None
+            if side is not None and _on("WSIS_BRANCH_LOSS", "0"):      # (measured: within the noise)
                 main = torch.cuda.current_stream()
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
@@ -68,14 +111,13 @@ class MultiTaskLoss(nn.Module):
                                                                          self.ignore_label)
                 semantic_scores.record_stream(side)
                 semantic_labels.record_stream(side)
-                loss_join = (main, side, (semantic_loss, n_kept))
+                join = (main, side, (semantic_loss, n_kept))
             else:
                 semantic_loss, n_kept = wsis_ops.semantic_point_loss(semantic_scores, semantic_labels, self.ignore_label)
-                loss_join = None
             loss_out["semantic_loss"] = (semantic_loss, n_kept)
-        else:
-            semantic_loss = self.semantic_criterion(semantic_scores, semantic_labels)
-        if self.semantic_dice and not fused:
+            return semantic_loss, join
+        semantic_loss = self.semantic_criterion(semantic_scores, semantic_labels)
+        if self.semantic_dice:
             keep = semantic_labels != self.ignore_label
             if indexed:
                 semantic_scores = F.softmax(semantic_scores[keep], dim=-1)
@@ -87,140 +129,97 @@ class MultiTaskLoss(nn.Module):
                 one_hot = F.one_hot(torch.where(keep, semantic_labels, torch.zeros_like(semantic_labels)),
                                     num_classes=self.semantic_class_num) * w
             semantic_loss = semantic_loss + dice_loss_multi_classes(semantic_scores, one_hot).mean()
-        if not fused:
-            loss_out["semantic_loss"] = (semantic_loss, semantic_scores.sum())
+        loss_out["semantic_loss"] = (semantic_loss, semantic_scores.sum())
+        return semantic_loss, None
 
-        joint = epoch > self.joint_training_epoch
-        if joint:
-            sp_sem_labels, sp_ins_labels = loss_inp["superpoint_labels"]
-            # the validity mask and its count: only the unfused branches read them (the fused kernels take the two label
-            # tensors), so they are formed on first use -- four launches the default device path never needs
-            _mask = []
-
-            def _valid():
-                if not _mask:
-                    m = (sp_ins_labels != self.ignore_label) & (sp_sem_labels != self.ignore_label)
-                    _mask.extend([m, m.sum()])
-                return _mask
-
-            sp_semantic_scores = loss_inp["sp_semantic"]
-            if (not indexed and sp_semantic_scores.is_cuda and sp_semantic_scores.dim() == 2
-                    and sp_semantic_scores.shape[1] <= 32 and sp_semantic_scores.shape[0] >= 1 and os.environ.get("WSIS_FUSE_SP_CE", "1") != "0"):
-                import wsis_ops      # cross entropy + the logged sum of the scores: one launch each way (csrc/loss.hip)
-                superpoint_semantic_loss, sp_score_sum = wsis_ops.superpoint_cross_entropy(
-                    sp_semantic_scores, sp_sem_labels, self.ignore_label)
-            else:
-                superpoint_semantic_loss = self.superpoint_semantic_criterion(sp_semantic_scores, sp_sem_labels)
-                sp_score_sum = sp_semantic_scores.sum()
-            loss_out["superpoint_semantic_loss"] = (superpoint_semantic_loss, sp_score_sum)
-
-            fused_reg = (not indexed and self.supervise_sp_offset and self.supervise_instance_size
-                         and loss_inp["sp_offset_vector"][0].is_cuda
-                         and os.environ.get("WSIS_FUSE_SP_LOSS", "1") != "0")
-            if fused_reg:   # offset L1 + cosine, occupancy and size L1 in one launch (csrc/loss.hip)
-                import wsis_ops
-                pred_off, gt_off = loss_inp["sp_offset_vector"]
-                pred_occ, gt_occ = loss_inp["sp_occupancy"]
-                pred_size, gt_size = loss_inp["sp_instance_size"]
-                offset_norm_loss, offset_dir_loss, occupancy_loss, instance_size_loss, n_reg = \
-                    wsis_ops.sp_regression_losses(pred_off, gt_off, pred_occ, gt_occ, pred_size, gt_size,
-                                                  sp_sem_labels, sp_ins_labels, self.ignore_label)
-                loss_out["offset_norm_loss"] = (offset_norm_loss, n_reg)
-                loss_out["offset_dir_loss"] = (offset_dir_loss, n_reg)
-
-            if self.supervise_sp_offset and not fused_reg:
-                pred_off, gt_off = loss_inp["sp_offset_vector"]
-                pt_dist = torch.sum(torch.abs(pred_off - gt_off), dim=-1)
-                sp_valid, n_valid = _valid()
-                offset_norm_loss = torch.sum(pt_dist * sp_valid) / (n_valid + 1e-6)
-                gt_dir = gt_off / (torch.norm(gt_off, p=2, dim=1).unsqueeze(-1) + 1e-8)
-                pt_dir = pred_off / (torch.norm(pred_off, p=2, dim=1).unsqueeze(-1) + 1e-8)
-                direction_diff = -(gt_dir * pt_dir).sum(-1)
-                offset_dir_loss = torch.sum(direction_diff * sp_valid) / (n_valid + 1e-6)
-                loss_out["offset_norm_loss"] = (offset_norm_loss, n_valid)
-                loss_out["offset_dir_loss"] = (offset_dir_loss, n_valid)
-
-            feats, sp_batch_offsets = loss_inp["sp_discriminative_features"]
-            offs = [int(o) for o in sp_batch_offsets]
-            slots = loss_inp.get("sp_instance_slots")      # host-known bound of the instance ids per scene (optional)
-            d_losses = []
-            for i in range(1, len(offs)):
-                b, e = offs[i - 1], offs[i]
-                if indexed:
-                    valid = _valid()[0][b:e]
-                    d_loss, _, _, _ = self.discriminative_loss(feats[b:e][valid], sp_ins_labels[b:e][valid])
-                elif (slots is not None and feats.is_cuda and 1 <= int(slots[i - 1]) <= 64 and 1 <= e - b <= 4096
-                      and self.discriminative_feature_dim == 7 and os.environ.get("WSIS_FUSE_DISC_LOSS", "1") != "0"):
-                    import wsis_ops          # one launch each way (csrc/loss.hip)
-                    d_loss = wsis_ops.discriminative_loss(feats[b:e], sp_ins_labels[b:e], sp_sem_labels[b:e],
-                                                          int(slots[i - 1]), self.ignore_label, self.delta_v,
-                                                          self.delta_d, self.param_var, self.param_dist, self.param_reg)
-                elif slots is not None and 1 <= int(slots[i - 1]) <= 512:
-                    d_loss = self.discriminative_loss_slots(feats[b:e], sp_ins_labels[b:e], _valid()[0][b:e],
-                                                            int(slots[i - 1]))
-                else:
-                    d_loss = self.discriminative_loss_masked(feats[b:e], sp_ins_labels[b:e], _valid()[0][b:e])
-                d_losses.append(d_loss.view(-1))
-            # mean over the scenes; one scene: the mean of one value is that value (x / 1 is exact)
-            sp_d_loss = torch.mean(torch.cat(d_losses)) if len(d_losses) != 1 else d_losses[0].reshape(())
-            loss_out["superpoint_discriminative_loss"] = (sp_d_loss, feats.shape[0])
-
-            if fused_reg:
-                loss_out["occupancy_loss"] = (occupancy_loss, n_reg)
-                loss_out["instance_size_loss"] = (instance_size_loss, n_reg)
-            elif self.supervise_instance_size:
-                pred_occ, gt_occ = loss_inp["sp_occupancy"]
-                pred_size, gt_size = loss_inp["sp_instance_size"]
-                sp_valid, n_valid = _valid()
-                if indexed:
-                    occupancy_loss = self.occupany_L1loss(pred_occ[sp_valid], gt_occ[sp_valid])
-                    instance_size_loss = self.instance_size_L1loss(pred_size[sp_valid], gt_size[sp_valid])
-                else:
-                    occupancy_loss = _masked_l1(pred_occ, gt_occ, sp_valid)
-                    instance_size_loss = _masked_l1(pred_size, gt_size, sp_valid)
-                loss_out["occupancy_loss"] = (occupancy_loss, n_valid)
-                loss_out["instance_size_loss"] = (instance_size_loss, n_valid)
-
-        # losses_3D_WSIS.py:130-151: loss = 0.0 + 1.0 * term + ...  All weights are 1.0 there, and 0.0 + x and 1.0 * x are
-        # exact in floating point: the same sum in the same order without the seven scalar multiplications (each one a
-        # launch forward and one backward)
-        if fused and loss_join is not None:       # the point term joins the others here
-            main, side, made = loss_join
-            main.wait_stream(side)
-            for t in made:
-                t.record_stream(main)
-        # (the terms and the pairs of the reference's expression; summed left to right)
-        terms, paired = [semantic_loss], 0
-        self._log("point semantic loss", semantic_loss)
-        if joint:
-            terms.append(superpoint_semantic_loss)
-            self._log("sp semantic loss", superpoint_semantic_loss)
-            if self.supervise_sp_offset:
-                paired |= 1 << len(terms)                  # loss + (offset_norm_loss + offset_dir_loss)
-                terms += [offset_norm_loss, offset_dir_loss]
-                self._log("sp offset norm loss", offset_norm_loss)
-                self._log("sp offset dir loss", offset_dir_loss)
-            terms.append(sp_d_loss)
-            self._log("sp discriminative loss", sp_d_loss)
-            if self.supervise_instance_size:
-                terms += [occupancy_loss, instance_size_loss]
-                self._log("sp occupancy loss", occupancy_loss)
-                self._log("sp instance size loss", instance_size_loss)
-        if (len(terms) > 1 and len(terms) <= 8 and all(torch.is_tensor(t) and t.is_cuda and t.numel() == 1 for t in terms)
-                and os.environ.get("WSIS_FUSE_LOSS_SUM", "1") != "0"):
-            import wsis_ops
-            loss = wsis_ops.loss_sum(terms, paired)      # one launch instead of one per `loss = loss + term`
+    def _sp_semantic(self, inp, indexed, loss_out):
+        """CrossEntropy(ignore_index) of the superpoint scores, logged with their sum"""
+        scores, sp_sem_labels = inp["sp_semantic"], inp["superpoint_labels"][0]
+        if (not indexed and scores.is_cuda and scores.dim() == 2 and scores.shape[0] >= 1
+                and _on("WSIS_FUSE_SP_CE") and scores.shape[1] <= _ops().LOSS_MAX_CLASSES):
+            # cross entropy + the logged sum of the scores: one launch each way (csrc/loss.hip)
+            loss, score_sum = _ops().superpoint_cross_entropy(scores, sp_sem_labels, self.ignore_label)
         else:
-            loss = terms[0]
-            i = 1
-            while i < len(terms):
-                if (paired >> i) & 1:
-                    loss = loss + (terms[i] + terms[i + 1])
-                    i += 2
-                else:
-                    loss = loss + terms[i]
-                    i += 1
-        return loss, loss_out
+            loss = self.superpoint_semantic_criterion(scores, sp_sem_labels)
+            score_sum = scores.sum()
+        loss_out["superpoint_semantic_loss"] = (loss, score_sum)
+        return loss
+
+    def _sp_regression(self, inp, indexed, valid):
+        """offset L1, offset cosine, occupancy L1 and instance-size L1 over the labelled superpoints and their number
+        (None for a term that is not supervised)"""
+        if (not indexed and self.supervise_sp_offset and self.supervise_instance_size
+                and inp["sp_offset_vector"][0].is_cuda and _on("WSIS_FUSE_SP_LOSS")):
+            return _ops().sp_regression_losses(      # all four in one launch (csrc/loss.hip)
+                *inp["sp_offset_vector"], *inp["sp_occupancy"], *inp["sp_instance_size"], *inp["superpoint_labels"],
+                self.ignore_label)
+        sp_valid, n_valid = valid()
+        offset_norm_loss = offset_dir_loss = occupancy_loss = instance_size_loss = None
+        if self.supervise_sp_offset:
+            pred_off, gt_off = inp["sp_offset_vector"]
+            pt_dist = torch.sum(torch.abs(pred_off - gt_off), dim=-1)
+            offset_norm_loss = torch.sum(pt_dist * sp_valid) / (n_valid + 1e-6)
+            gt_dir = gt_off / (torch.norm(gt_off, p=2, dim=1).unsqueeze(-1) + 1e-8)
+            pt_dir = pred_off / (torch.norm(pred_off, p=2, dim=1).unsqueeze(-1) + 1e-8)
+            direction_diff = -(gt_dir * pt_dir).sum(-1)
+            offset_dir_loss = torch.sum(direction_diff * sp_valid) / (n_valid + 1e-6)
+        if self.supervise_instance_size:
+            pred_occ, gt_occ = inp["sp_occupancy"]
+            pred_size, gt_size = inp["sp_instance_size"]
+            if indexed:
+                occupancy_loss = self.occupany_L1loss(pred_occ[sp_valid], gt_occ[sp_valid])
+                instance_size_loss = self.instance_size_L1loss(pred_size[sp_valid], gt_size[sp_valid])
+            else:
+                occupancy_loss = _masked_l1(pred_occ, gt_occ, sp_valid)
+                instance_size_loss = _masked_l1(pred_size, gt_size, sp_valid)
+        return offset_norm_loss, offset_dir_loss, occupancy_loss, instance_size_loss, n_valid
+
+    def _sp_discriminative(self, inp, indexed, valid, loss_out):
+        """mean over the scenes of the pull / push / reg loss of their superpoint embeddings"""
+        feats, sp_batch_offsets = inp["sp_discriminative_features"]
+        sp_sem_labels, sp_ins_labels = inp["superpoint_labels"]
+        offs = [int(o) for o in sp_batch_offsets]
+        slots = inp.get("sp_instance_slots")      # host-known bound of the instance ids per scene (optional)
+        d_losses = []
+        for i in range(1, len(offs)):
+            b, e = offs[i - 1], offs[i]
+            n_slots = int(slots[i - 1]) if slots is not None else 0
+            ins = sp_ins_labels[b:e]
+            if indexed:
+                keep = valid()[0][b:e]
+                d_loss, _, _, _ = self.discriminative_loss(feats[b:e][keep], ins[keep])
+            elif (feats.is_cuda and self.discriminative_feature_dim == 7 and _on("WSIS_FUSE_DISC_LOSS")
+                  and 1 <= n_slots <= _ops().DISC_MAX_SLOTS and 1 <= e - b <= _ops().DISC_MAX_ROWS):
+                # one launch each way (csrc/loss.hip)
+                d_loss = _ops().discriminative_loss(feats[b:e], ins, sp_sem_labels[b:e], n_slots, self.ignore_label,
+                                                    self.delta_v, self.delta_d, self.param_var, self.param_dist,
+                                                    self.param_reg)
+            elif 1 <= n_slots <= 512:
+                d_loss = self.discriminative_loss_slots(feats[b:e], ins, valid()[0][b:e], n_slots)
+            else:
+                d_loss = self.discriminative_loss_masked(feats[b:e], ins, valid()[0][b:e])
+            d_losses.append(d_loss.view(-1))
+        # mean over the scenes; one scene: the mean of one value is that value (x / 1 is exact)
+        sp_d_loss = torch.mean(torch.cat(d_losses)) if len(d_losses) != 1 else d_losses[0].reshape(())
+        loss_out["superpoint_discriminative_loss"] = (sp_d_loss, feats.shape[0])
+        return sp_d_loss
+
+    def _sum_terms(self, terms, paired):
+        """the terms and the pairs of the reference's expression (losses_3D_WSIS.py:130-151: loss = 0.0 + 1.0 * term +
+        ...), summed left to right.  All weights are 1.0 there, and 0.0 + x and 1.0 * x are exact in floating point: the
+        same sum in the same order without the seven scalar multiplications (each one a launch forward and one backward)"""
+        for name, t in terms:
+            self._log(name, t)
+        terms = [t for _, t in terms]
+        if (len(terms) > 1 and all(torch.is_tensor(t) and t.is_cuda and t.numel() == 1 for t in terms)
+                and _on("WSIS_FUSE_LOSS_SUM") and len(terms) <= _ops().LOSS_SUM_MAX_TERMS):
+            return _ops().loss_sum(terms, paired)      # one launch instead of one per `loss = loss + term`
+        loss, i = terms[0], 1
+        while i < len(terms):
+            pair = (paired >> i) & 1       # bit i: loss + (t_i + t_i+1)
+            loss = loss + ((terms[i] + terms[i + 1]) if pair else terms[i])
+            i += 1 + pair
+        return loss
 
     def discriminative_loss(self, prediction, correct_label):
         """pull (delta_v) / push (L1 cdist, delta_d) / reg terms over the instances of one scene

@@ -1092,6 +1092,8 @@ def sp_regression_losses(pred_off, gt_off, pred_occ, gt_occ, pred_size, gt_size,
                                    ignore_label)
 
 
+# limits of the kernels in csrc/loss.hip (LOSS_CMAX, wsis_loss_sum's terms, DL_ROWS, DL_SLOTS): callers choose by them
+LOSS_MAX_CLASSES, LOSS_SUM_MAX_TERMS = 32, 8
 DISC_MAX_ROWS, DISC_MAX_SLOTS = 4096, 64
 
 
