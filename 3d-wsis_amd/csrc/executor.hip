@@ -6,7 +6,6 @@
 // Every op maps 1:1 onto the single-op entry points of this library (same kernels, same summation orders, so the
 // results are bit-identical to calling them one by one); CAT / SPLIT / ADD are the elementwise glue of the UNet
 // (torch.cat of the skip connection, its backward, gradient accumulation at the residual fan-out).
-#include <optional>
 #include <condition_variable>
 #include <cstdlib>
 #include <deque>
@@ -307,49 +306,58 @@ DwWorker& dw_worker() {
   static DwWorker* w = new DwWorker();      // never destroyed: its thread may outlive static destruction
   return *w;
 }
-bool dw_thread_enabled() {
-  const char* e = tune_env("WSIS_DW_THREAD");
-  return e ? atoi(e) != 0 : true;
-}
-
-// deferred slab sums (one dw2_reduce_batch launch per part of a pass instead of one small launch per product); read per
-// pass.  Off while the profiler brackets every product with events: a product's duration then includes its own sum.
-// Measured (tools/r06_ab_reduce.sh, profiles/r06_ab_reduce_c*.txt): bit-identical and SLOWER in the step -- 7.75 -> 7.90 ms
-// at one scene, 20.36 -> 20.42 at four: the per-product sums hide under the dIn products as they go, the batched launch
-// reads every slab of the pass from HBM (0.44 GB at one scene) at the end of the pass, in front of the join.  Opt-in.
-bool dw_batch_reduce_enabled() {
-  const char* e = getenv("WSIS_DW_BATCH_REDUCE");
-  return (e ? atoi(e) != 0 : false) && !g_prof_on;
-}
-
-// The weight gradient of the LAST op of a pass that has no dIn product of its own (the input convolution: its dY is the
-// final result of the main stream's chain) goes on the CALLER's stream: the main stream has nothing left to run, so the
-// product overlaps the previous layer's weight gradient still running on the side stream instead of queueing behind it
-// -- the tail of a backward pass that nothing hides (one scene: ~55 us of a 7.8 ms step).  Its slabs use the op workspace
-// (free: the op issues nothing else).  WSIS_DW_TAIL_MAIN=0 (read per pass): everything on the side stream.
-bool dw_tail_main_enabled() {
-  const char* e = getenv("WSIS_DW_TAIL_MAIN");
-  return e ? atoi(e) != 0 : true;
+// ---- every switch of a pass, read ONCE per call (the tests and bench.py flip them between passes)
+struct PassOptions {
+  bool fwd2;              // WSIS_FWD2=0: every convolution on spconv_fwd_kernel, none on the wave-autonomous kernel (spconv2.hip)
+  bool dw_stream;         // WSIS_DW_STREAM=0: everything on the caller's stream (bench.py's event-instrumented roofline steps)
+  bool dw_thread;         // WSIS_DW_THREAD=0: the side-stream calls come from the caller's thread
+  // WSIS_DW_BATCH_REDUCE=1: deferred slab sums, one dw2_reduce_batch launch per part of a pass instead of one small launch
+  // per product.  Measured (profiles/r06_ab_reduce_c*.txt): bit-identical and SLOWER in the step -- 7.75 -> 7.90 ms at one
+  // scene, 20.36 -> 20.42 at four: the per-product sums hide under the dIn products as they go, the batched launch reads
+  // every slab of the pass from HBM (0.44 GB at one scene) at the end of the pass, in front of the join.  Opt-in.
+  bool dw_batch_reduce;
+  // The weight gradient of the LAST op of a pass that has no dIn product of its own (the input convolution: its dY is the
+  // final result of the main stream's chain) goes on the CALLER's stream: the main stream has nothing left to run, so the
+  // product overlaps the previous layer's weight gradient still running on the side stream instead of queueing behind it
+  // (one scene: ~55 us of a 7.8 ms step).  Its slabs use the op workspace.  WSIS_DW_TAIL_MAIN=0: all on the side stream.
+  bool dw_tail_main;
+  bool wt_side;           // WSIS_WT_SIDE=0: the weight transposes on the caller's stream
+  // WSIS_DW_EARLY: a weight gradient forked in FRONT of its op's dIn launch (measured in-process: 7.69 -> 7.50 ms at one
+  // scene per step, 11.70 -> 11.50 at two, 20.11 -> 20.22 at four -- with a batch that fills the GPU the early product takes
+  // from the dIn launch beside it what it gains at the tail; default: by the batch hint, below WSIS_DW_EARLY_ROWS voxels)
+  bool dw_early;
+  bool slab_bn_partials;  // WSIS_SLAB_BN_PARTIALS=1: slab-split dIn products write the BatchNorm partials too
+  bool prof;              // the profiler brackets products with events: single-threaded, no deferred sums, no forks of W^T
+  bool capturing;         // the caller's stream is being captured into a graph
+  // (off while the profiler is on: a product's duration then includes its own sum)
+  bool dw_defer() const { return dw_batch_reduce && !prof; }
+};
+inline bool env_flag(const char* e, bool dflt) { return e ? atoi(e) != 0 : dflt; }
+// st == nullptr: a size query (no stream to ask)
+PassOptions read_pass_options(const hipStream_t* st) {
+  PassOptions o;
+  o.fwd2 = env_flag(getenv("WSIS_FWD2"), true);
+  o.dw_stream = env_flag(getenv("WSIS_DW_STREAM"), true);
+  o.dw_thread = env_flag(tune_env("WSIS_DW_THREAD"), true);
+  o.dw_batch_reduce = env_flag(getenv("WSIS_DW_BATCH_REDUCE"), false);
+  o.dw_tail_main = env_flag(getenv("WSIS_DW_TAIL_MAIN"), true);
+  o.wt_side = env_flag(getenv("WSIS_WT_SIDE"), true);
+  const char* rows = getenv("WSIS_DW_EARLY_ROWS");
+  o.dw_early = env_flag(getenv("WSIS_DW_EARLY"), dw2_batch_rows() < (rows ? atoll(rows) : 500000));
+  o.slab_bn_partials = env_flag(getenv("WSIS_SLAB_BN_PARTIALS"), false);
+  o.prof = g_prof_on;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  o.capturing = st && (hipStreamIsCapturing(*st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone);
+  return o;
 }
 inline bool dw_tail_on_main(const wsis_op* ops, int n, int i) {
   return i == n - 1 && ops[i].kind == WSIS_OP_CONV_BWD && ops[i].out[1] && !ops[i].out[0];
-}
-
-bool dw_stream_enabled() {   // read per pass: bench.py switches it off for its event-instrumented roofline steps
-  const char* e = getenv("WSIS_DW_STREAM");
-  return e ? atoi(e) != 0 : true;
 }
 
 inline int64_t wt_bytes_of(const wsis_op& op) {
   return up((int64_t)op.K * op.Cin * op.Cout * (int64_t)sizeof(float));
 }
 
-// wave-autonomous kernel (csrc/spconv2.hip) for a product with Cin input and Cout output channels; WSIS_FWD2=0 keeps
-// every convolution on spconv_fwd_kernel
-bool fwd2_enabled() {
-  const char* e = getenv("WSIS_FWD2");
-  return e ? atoi(e) != 0 : true;
-}
 inline bool use_fwd2(const wsis_op& op, bool on) {
   // 32-bit gather offsets: the gathered tensor (input of the forward pass, dY of the dIn pass) stays below 2 GiB
   const int64_t gathered = op.kind == WSIS_OP_CONV ? op.M_in * op.Cin : op.M_out * op.Cout;
@@ -436,6 +444,65 @@ int64_t op_ws_bytes(const wsis_op& op, bool on) {
   }
 }
 
+// the BatchNorm backward op that takes the slice partials of dIn op i: dX is the dy of a BatchNorm backward a few ops on
+// (WSIS_OP_BN_RELU_BWD with in[1] == this dX, flagged too); the dIn epilogue also makes that op's reduction, into its in[7]
+inline int paired_bn(const wsis_op* ops, int n, int i) {
+  const wsis_op& op = ops[i];
+  for (int j = i + 1; j < n && j <= i + 4; ++j)
+    if (ops[j].kind == WSIS_OP_BN_RELU_BWD && ops[j].in[1] == op.out[0] && (ops[j].flags & WSIS_OPF_STATS)) return j;
+  return -1;
+}
+
+// ---- the workspace of a pass, decided from the op list alone before anything is enqueued (plan_pass).  Five regions in
+// this order, each a multiple of ALIGN: the 16-bit B^T weights | the transposed fp32 weights | the weight-gradient slabs
+// (shared by the dW launches, which are ordered among themselves on one stream -- or, with deferred slab sums, one region
+// per product: its slabs live until the batched launch that sums them) | phase table + slabs of the resident deep-level
+// launches (0 in the default build) | the per-op workspace (the largest op's; a run hands its ops all that is left)
+struct PassPlan {
+  enum { LP, WT, DW, DEEP, OP, REGIONS };
+  int64_t at[REGIONS], bytes[REGIONS], total = 0;
+  std::vector<int64_t> lp_off, wt_off;      // per op: its weights in the LP / WT region (-1: the op has none there)
+  int64_t dw_max = 0;                        // slabs of the largest weight-gradient product
+  int n_dw = 0;                              // weight-gradient products of the pass
+};
+
+// ---- a pass being issued.  Once a fork has been recorded finish() is the only way out: it orders the caller's stream
+// behind everything the pass put on the side stream, on every exit path.
+struct PassRun {
+  const wsis_op* ops;
+  int n, mark_op;
+  void *d_sync, *stream, *waiter_stream;
+  hipStream_t st;
+  PassOptions opt;
+  PassPlan plan;
+  char *base, *ws;                   // the caller's workspace; its per-op region
+  int64_t ws_bytes;                  // of ws: everything behind the first four regions
+  SideStream* side = nullptr;        // weight gradients (nullptr: on the caller's stream)
+  SideStream* wt_side = nullptr;     // weight transposes (nullptr: on the caller's stream)
+  bool wt_pending = false;           // the caller's stream has not waited for the transposes yet
+  bool forked = false;               // a weight gradient of this part went to the side stream
+  // the side-stream calls of the pass from a second host thread (not under stream capture, not while the profiler's
+  // event lists are being filled: those are single-threaded)
+  bool use_worker = false, worker_busy = false;
+  int cur_dev = 0;
+  // record slots of the pass's deferred products (stable addresses: the worker thread fills them) and what has been
+  // flushed so far; the vector outlives every task that points into it (drained before finish() returns)
+  std::vector<DwRedRec> dw_recs;
+  int dw_next = 0, dw_flushed = 0;
+  int64_t dw_off = 0;
+  std::vector<char> bn_unfused;      // BatchNorm backward ops whose dIn pass did not write partials this run
+
+  char* region(int k) const { return base + plan.at[k]; }
+  const float* wt_of(int i) const { return reinterpret_cast<const float*>(region(PassPlan::WT) + plan.wt_off[i]); }
+  int start();
+  int fork_weight_transposes();
+  int await_transposes_before(int i);
+  int dw_issue(const wsis_op& op);
+  int dw_flush();
+  int drain_worker();
+  int milestone();
+  int finish(int first_err, bool defer_join);
+};
 
 #if WSIS_EXPERIMENTAL      // (make EXPERIMENTAL=1: the retired designs of DESIGN.md section 8)
 // ---- resident deep-level kernel (deep.hip): which ops of a pass can run as phases of ONE launch ------------------------
@@ -448,14 +515,6 @@ inline int64_t deep_rows(const wsis_op& op) {
   }
 }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// the BatchNorm backward op that takes the slice partials of dIn op i (see run_ops_impl)
-inline int paired_bn(const wsis_op* ops, int n, int i) {
-  const wsis_op& op = ops[i];
-  for (int j = i + 1; j < n && j <= i + 4; ++j)
-    if (ops[j].kind == WSIS_OP_BN_RELU_BWD && ops[j].in[1] == op.out[0] && (ops[j].flags & WSIS_OPF_STATS)) return j;
-  return -1;
-}
 
 bool deep_op_ok(const wsis_op* ops, int n, int i, bool fwd2_on) {
   const wsis_op& op = ops[i];
@@ -564,15 +623,103 @@ int64_t deep_ws_bytes(const wsis_op* ops, int n, bool fwd2_on) {
   return best;
 }
 
-// phases of ops [i0, i1) -> table; wt_base / wt_off: the transposed weights of the pass; slab: private slab regions
+// the phase table of a resident run under construction; wt_base / wt_off: the transposed weights of the pass; slab: the
+// next free byte of the run's private slab regions
+struct DeepBuild {
+  const char* wt_base;
+  const std::vector<int64_t>& wt_off;
+  char* slab;
+  bool stamps;
+  std::vector<DeepOp>& tab;
+  std::vector<std::pair<int, std::pair<int, int>>>& conv_stamps;
+  void push(DeepOp& d) {
+    d.stamp = stamps ? (int)tab.size() + 1 : -1;
+    tab.push_back(d);
+  }
+};
+
+// the phases of a forward or dIn product (op i): the product and, with offset slabs, the sum that finishes it
+int deep_build_conv(DeepBuild& b, const wsis_op* ops, int n, int i) {
+  const wsis_op& op = ops[i];
+  DeepOp d{};
+  const bool fwd = op.kind == WSIS_OP_CONV;
+  if (!fwd && !op.out[0]) return WSIS_OK;      // weight gradient only: no phase
+  const int64_t Mo = fwd ? op.M_out : op.M_in, Mg = fwd ? op.M_in : op.M_out;
+  const int Ci = fwd ? op.Cin : op.Cout, Co = fwd ? op.Cout : op.Cin;
+  int nw = 1, zs = 1;
+  if (!deep_conv_plan(Mo, op.K, Ci, Co, &nw, &zs)) return fail(WSIS_ERR_ARG, "deep: op %d has no plan", i);
+  d.kind = DK_CONV;
+  d.NW = nw;
+  d.ZS = zs;
+  d.K = op.K;
+  d.Cin = Ci;
+  d.Cout = Co;
+  d.M_in = Mg;
+  d.M_out = Mo;
+  d.x_bytes = (uint32_t)(Mg * Ci * 4);
+  const void* stats = nullptr;
+  DeepOp epi{};
+  if (fwd) {
+    d.p[0] = op.in[0];
+    d.p[1] = op.in[1];
+    d.p[2] = op.in[2];
+    d.p[3] = b.wt_base + b.wt_off[i];
+    d.p[4] = op.in[4];
+    d.p[5] = op.in[5];
+    d.p[6] = op.out[0];
+    d.flip = 0;
+    if (op.flags & WSIS_OPF_STATS) stats = op.out[1];
+  } else {
+    d.p[0] = op.in[2];
+    d.p[1] = op.in[5];
+    d.p[2] = op.in[6];
+    d.p[3] = op.in[1];
+    d.p[6] = op.out[0];
+    d.flip = (op.flags & WSIS_OPF_FLIP) ? 1 : 0;
+    if (op.flags & WSIS_OPF_STATS) {
+      const wsis_op& bn = ops[paired_bn(ops, n, i)];
+      stats = bn.in[7];
+      epi.p[9] = bn.in[0];
+      epi.p[10] = bn.in[2];
+      epi.p[11] = bn.in[3];
+      epi.p[12] = bn.in[4];
+      epi.p[13] = bn.in[5];
+      epi.eps = bn.eps;
+      epi.relu = (bn.flags & WSIS_OPF_RELU) ? 1 : 0;
+    }
+  }
+  WSIS_REQUIRE(d.p[1] || (op.K == 1 && Mg == Mo), "nbr may be null only for the dense 1x1 case");
+  const int s0 = (int)b.tab.size();
+  if (zs > 1) {
+    DeepOp r = d;              // the b.slab sum finishes the product: bias / residual / partials move there
+    d.p[7] = b.slab;
+    d.p[4] = d.p[5] = nullptr;
+    b.push(d);
+    r.kind = DK_REDUCE;
+    r.p[7] = b.slab;
+    r.p[8] = stats;
+    for (int k = 9; k <= 13; ++k) r.p[k] = epi.p[k];
+    r.eps = epi.eps;
+    r.relu = epi.relu;
+    b.push(r);
+    b.slab += up((int64_t)zs * Mo * Co * 4);
+  } else {
+    d.p[8] = stats;
+    for (int k = 9; k <= 13; ++k) d.p[k] = epi.p[k];
+    d.eps = epi.eps;
+    d.relu = epi.relu;
+    b.push(d);
+  }
+  b.conv_stamps.push_back({i, {s0, (int)b.tab.size()}});      // stamps s0 (start) .. s0 + 1 (main) .. size (product done)
+  return WSIS_OK;
+}
+
+// phases of ops [i0, i1) -> table
 int deep_build(const wsis_op* ops, int n, int i0, int i1, const char* wt_base, const std::vector<int64_t>& wt_off, char* slab,
                bool stamps, std::vector<DeepOp>& tab, std::vector<std::pair<int, std::pair<int, int>>>& conv_stamps) {
   tab.clear();
   conv_stamps.clear();
-  auto push = [&](DeepOp& d) {
-    d.stamp = stamps ? (int)tab.size() + 1 : -1;
-    tab.push_back(d);
-  };
+  DeepBuild b{wt_base, wt_off, slab, stamps, tab, conv_stamps};
   for (int i = i0; i < i1; ++i) {
     const wsis_op& op = ops[i];
     DeepOp d{};
@@ -581,75 +728,8 @@ int deep_build(const wsis_op* ops, int n, int i0, int i1, const char* wt_base, c
     switch (op.kind) {
       case WSIS_OP_CONV:
       case WSIS_OP_CONV_BWD: {
-        const bool fwd = op.kind == WSIS_OP_CONV;
-        if (!fwd && !op.out[0]) break;
-        const int64_t Mo = fwd ? op.M_out : op.M_in, Mg = fwd ? op.M_in : op.M_out;
-        const int Ci = fwd ? op.Cin : op.Cout, Co = fwd ? op.Cout : op.Cin;
-        int nw = 1, zs = 1;
-        if (!deep_conv_plan(Mo, op.K, Ci, Co, &nw, &zs)) return fail(WSIS_ERR_ARG, "deep: op %d has no plan", i);
-        d.kind = DK_CONV;
-        d.NW = nw;
-        d.ZS = zs;
-        d.K = op.K;
-        d.Cin = Ci;
-        d.Cout = Co;
-        d.M_in = Mg;
-        d.M_out = Mo;
-        d.x_bytes = (uint32_t)(Mg * Ci * 4);
-        const void* stats = nullptr;
-        DeepOp epi{};
-        if (fwd) {
-          d.p[0] = op.in[0];
-          d.p[1] = op.in[1];
-          d.p[2] = op.in[2];
-          d.p[3] = wt_base + wt_off[i];
-          d.p[4] = op.in[4];
-          d.p[5] = op.in[5];
-          d.p[6] = op.out[0];
-          d.flip = 0;
-          if (op.flags & WSIS_OPF_STATS) stats = op.out[1];
-        } else {
-          d.p[0] = op.in[2];
-          d.p[1] = op.in[5];
-          d.p[2] = op.in[6];
-          d.p[3] = op.in[1];
-          d.p[6] = op.out[0];
-          d.flip = (op.flags & WSIS_OPF_FLIP) ? 1 : 0;
-          if (op.flags & WSIS_OPF_STATS) {
-            const wsis_op& bn = ops[paired_bn(ops, n, i)];
-            stats = bn.in[7];
-            epi.p[9] = bn.in[0];
-            epi.p[10] = bn.in[2];
-            epi.p[11] = bn.in[3];
-            epi.p[12] = bn.in[4];
-            epi.p[13] = bn.in[5];
-            epi.eps = bn.eps;
-            epi.relu = (bn.flags & WSIS_OPF_RELU) ? 1 : 0;
-          }
-        }
-        WSIS_REQUIRE(d.p[1] || (op.K == 1 && Mg == Mo), "nbr may be null only for the dense 1x1 case");
-        const int s0 = (int)tab.size();
-        if (zs > 1) {
-          DeepOp r = d;              // the slab sum finishes the product: bias / residual / partials move there
-          d.p[7] = slab;
-          d.p[4] = d.p[5] = nullptr;
-          push(d);
-          r.kind = DK_REDUCE;
-          r.p[7] = slab;
-          r.p[8] = stats;
-          for (int k = 9; k <= 13; ++k) r.p[k] = epi.p[k];
-          r.eps = epi.eps;
-          r.relu = epi.relu;
-          push(r);
-          slab += up((int64_t)zs * Mo * Co * 4);
-        } else {
-          d.p[8] = stats;
-          for (int k = 9; k <= 13; ++k) d.p[k] = epi.p[k];
-          d.eps = epi.eps;
-          d.relu = epi.relu;
-          push(d);
-        }
-        conv_stamps.push_back({i, {s0, (int)tab.size()}});      // stamps s0 (start) .. s0 + 1 (main) .. size (product done)
+        const int rc = deep_build_conv(b, ops, n, i);
+        if (rc != WSIS_OK) return rc;
         break;
       }
       case WSIS_OP_BN_RELU: {
@@ -673,7 +753,7 @@ int deep_build(const wsis_op* ops, int n, int i0, int i1, const char* wt_base, c
         d.p[7] = op.out[0];
         d.p[8] = op.out[1];
         d.p[9] = op.out[2];
-        push(d);
+        b.push(d);
         break;
       }
       case WSIS_OP_BN_RELU_BWD:
@@ -693,7 +773,7 @@ int deep_build(const wsis_op* ops, int n, int i0, int i1, const char* wt_base, c
         d.p[8] = op.out[0];
         d.p[9] = op.out[1];
         d.p[10] = op.out[2];
-        push(d);
+        b.push(d);
         break;
       case WSIS_OP_CAT:
         d.kind = DK_CAT;
@@ -703,7 +783,7 @@ int deep_build(const wsis_op* ops, int n, int i0, int i1, const char* wt_base, c
         d.p[0] = op.in[0];
         d.p[1] = op.in[1];
         d.p[2] = op.out[0];
-        push(d);
+        b.push(d);
         break;
       case WSIS_OP_SPLIT:
         d.kind = DK_SPLIT;
@@ -713,7 +793,7 @@ int deep_build(const wsis_op* ops, int n, int i0, int i1, const char* wt_base, c
         d.p[0] = op.in[0];
         d.p[1] = op.out[0];
         d.p[2] = op.out[1];
-        push(d);
+        b.push(d);
         break;
       default:
         return fail(WSIS_ERR_ARG, "deep: op %d of kind %d is not a phase", i, op.kind);
@@ -722,9 +802,581 @@ int deep_build(const wsis_op* ops, int n, int i0, int i1, const char* wt_base, c
   return WSIS_OK;
 }
 
+// ops [i, *next) as ONE resident launch when a run of at least kDeepMinOps eligible ops starts at i; their weight
+// gradients follow on the side stream.  *next == i: no run starts here, op i is issued on its own
+int deep_issue_run(PassRun& r, int i, int* next) {
+  *next = i;
+  if (r.plan.bytes[PassPlan::DEEP] == 0 || !r.d_sync || r.opt.capturing || !deep_op_ok(r.ops, r.n, i, r.opt.fwd2)) return WSIS_OK;
+  const int i1 = deep_run_end(r.ops, r.n, i, r.mark_op >= i ? r.mark_op : -1, r.opt.fwd2);
+  if (i1 - i < kDeepMinOps) return WSIS_OK;
+  *next = i1;
+  std::vector<DeepOp> tab;
+  std::vector<std::pair<int, std::pair<int, int>>> convs;
+  char* const deep_ws = r.region(PassPlan::DEEP);
+  char* slab = deep_ws + deep_table_bytes(i1 - i);
+  int rc = deep_build(r.ops, r.n, i, i1, r.region(PassPlan::WT), r.plan.wt_off, slab, g_prof_on, tab, convs);
+  if (rc != WSIS_OK) return rc;
+  unsigned long long* d_stamps = nullptr;
+  if (g_prof_on && !tab.empty()) {
+    if (hipMalloc((void**)&d_stamps, (tab.size() + 1) * sizeof(unsigned long long)) != hipSuccess)
+      return fail(WSIS_ERR_HIP, "deep: stamp buffer allocation failed");
+    g_prof_bufs.push_back(d_stamps);
+  }
+  rc = deep_launch(tab.data(), (int)tab.size(), deep_ws, deep_sync_slot(r.d_sync), d_stamps, r.st);
+  if (rc != WSIS_OK) return rc;
+  if (d_stamps) {
+    if (g_deep_log.size() > 64) g_deep_log.clear();
+    g_deep_log.push_back({tab, d_stamps});
+    for (const auto& cs : convs) {
+      ProfRec p{};
+      p.d_stamps = d_stamps;
+      p.s0 = cs.second.first;
+      p.sm = cs.second.first + 1;
+      p.s1 = cs.second.second;
+      g_prof[0].push_back(p);
+    }
+  }
+  for (int k = i; k < i1 && rc == WSIS_OK; ++k)
+    if (r.ops[k].kind == WSIS_OP_CONV_BWD && r.ops[k].out[1]) rc = r.dw_issue(r.ops[k]);
+  return rc;
+}
+
+// a convolution that applies its input's BatchNorm as it reads (WSIS_OPF_BN_IN) and / or finishes the statistics of its
+// output inside the launch (WSIS_OPF_STAT_FIN)
+int issue_conv_fused_bn(PassRun& r, const wsis_op& op, int i) {
+  if (r.plan.wt_off[i] < 0)
+    return fail(WSIS_ERR_ARG, "op %d: fused BatchNorm requested from a convolution that is not on wsis_spconv_fwd_t", i);
+  wsis_bn_in bi;
+  bi.mean = (const float*)op.in[6];
+  bi.var = (const float*)op.in[7];
+  bi.gamma = (const float*)op.in[8];
+  bi.beta = (const float*)op.in[9];
+  bi.eps = op.eps;
+  bi.relu = (op.flags & WSIS_OPF_RELU) ? 1 : 0;
+  wsis_stat_target tg[2];
+  int nt = 0;
+  if (op.flags & WSIS_OPF_STAT_FIN) {
+    tg[0].mean = (float*)op.out[2];
+    tg[0].var = (float*)op.out[3];
+    tg[0].running_mean = (float*)const_cast<void*>(op.in[10]);
+    tg[0].running_var = (float*)const_cast<void*>(op.in[11]);
+    tg[0].momentum = op.momentum;
+    tg[0].reserved = 0;
+    nt = 1;
+    if (op.out[4]) {
+      tg[1].mean = (float*)op.out[4];
+      tg[1].var = (float*)op.out[5];
+      tg[1].running_mean = (float*)op.out[6];
+      tg[1].running_var = (float*)op.out[7];
+      tg[1].momentum = op.momentum2;
+      tg[1].reserved = 0;
+      nt = 2;
+    }
+  }
+  return wsis_spconv_fwd_f((const float*)op.in[0], (op.flags & WSIS_OPF_BN_IN) ? &bi : nullptr, (const int32_t*)op.in[1],
+                           (const int32_t*)op.in[2], r.wt_of(i), 0, (const float*)op.in[4], (const float*)op.in[5],
+                           (float*)op.out[0], (op.flags & WSIS_OPF_STATS) ? (float*)op.out[1] : nullptr, tg, nt, op.M_in,
+                           op.M_out, op.K, op.Cin, op.Cout, r.ws, r.ws_bytes, sync_slot(r.d_sync, i), r.stream);
+}
+
 #else
 inline int64_t deep_ws_bytes(const wsis_op*, int, bool) { return 0; }
+inline int deep_issue_run(PassRun&, int i, int* next) {
+  *next = i;
+  return WSIS_OK;
+}
+inline int issue_conv_fused_bn(PassRun&, const wsis_op&, int i) {
+  return fail(WSIS_ERR_ARG, "op %d: the fused BatchNorm forms of the convolution are in the EXPERIMENTAL build only", i);
+}
 #endif
+
+// The whole layout of a pass and every refusal that needs the op list alone.  The size query is this plus nothing; the
+// run takes its offsets from the same plan.  (The deferred-sum switch is read per pass: a pass whose workspace was sized
+// with it off and that runs with it on fails its size check.  The region is reserved whenever the switch is set,
+// profiler or not.)
+int plan_pass(const wsis_op* ops, int n, const PassOptions& o, PassPlan& p) {
+  p.lp_off.assign(n, -1);
+  p.wt_off.assign(n, -1);
+  int64_t lp = 0, wt = 0, dw_sum = 0, need = ALIGN;
+  for (int i = 0; i < n; ++i) {
+    const wsis_op& op = ops[i];
+    const char* why = lp_refusal(op);
+    if (why) return fail(WSIS_ERR_ARG, "wsis_run_ops: op %d: %s", i, why);
+    int64_t b = op_ws_bytes(op, o.fwd2);
+    if (b < 0) return fail(WSIS_ERR_ARG, "wsis_run_ops: op %d: a form this build does not run (fused BatchNorm: EXPERIMENTAL)", i);
+    if (dw_tail_on_main(ops, n, i)) b = std::max(b, dw_ws_of(op));      // (its slabs live in the op workspace)
+    need = std::max(need, b);
+    if (is_lp_conv(op)) {
+      p.lp_off[i] = lp;
+      lp += lp_wt_bytes_of(op);
+    }
+    if (needs_wt(op, o.fwd2)) {
+      if (!(op.kind == WSIS_OP_CONV ? op.in[3] : op.in[1]))
+        return fail(WSIS_ERR_ARG, "wsis_run_ops: op %d: convolution without weights", i);
+      p.wt_off[i] = wt;
+      wt += wt_bytes_of(op);
+    }
+    if (op.kind == WSIS_OP_CONV_BWD && op.out[1]) {
+      const int64_t d = dw_ws_of(op);
+      p.dw_max = std::max(p.dw_max, d);
+      dw_sum += d;
+      ++p.n_dw;
+    }
+  }
+  const int64_t sizes[PassPlan::REGIONS] = {lp, wt, o.dw_batch_reduce ? dw_sum : p.dw_max, deep_ws_bytes(ops, n, o.fwd2),
+                                            need + ALIGN};
+  p.total = 0;
+  for (int k = 0; k < PassPlan::REGIONS; ++k) {
+    p.at[k] = p.total;
+    p.bytes[k] = sizes[k];
+    p.total += sizes[k];
+  }
+  return WSIS_OK;
+}
+
+// The weights of the pass's convolutions into their slots base + off[i] (ops with off[i] < 0 have none), WT_MAX layers per
+// launch.  T = float: the transposed fp32 weights (dIn products flipped for submanifold tables).  T = a 16-bit word: the
+// B^T weights of the 16-bit convolutions, each rounded to its op's dtype -- a launch holds layers of one dtype.
+template <typename T>
+int launch_weight_batches(const wsis_op* ops, int n, const std::vector<int64_t>& off, char* base, hipStream_t st) {
+  constexpr bool lp = sizeof(T) == 2;
+  WtBatch b;
+  b.n = 0;
+  b.start[0] = 0;
+  int dtype = 0;
+  auto flush = [&]() -> int {
+    if (b.n == 0) return WSIS_OK;
+    if (!lp)
+      hipLaunchKernelGGL(weight_transpose_batch_kernel<float>, dim3(b.start[b.n]), dim3(256), 0, st, b);
+    else if (dtype == 0)
+      hipLaunchKernelGGL(weight_transpose_batch_kernel<__bf16>, dim3(b.start[b.n]), dim3(256), 0, st, b);
+    else
+      hipLaunchKernelGGL(weight_transpose_batch_kernel<_Float16>, dim3(b.start[b.n]), dim3(256), 0, st, b);
+    WSIS_LAUNCH_CHECK();
+    b.n = 0;
+    return WSIS_OK;
+  };
+  for (int i = 0; i < n; ++i) {
+    if (off[i] < 0) continue;
+    const wsis_op& op = ops[i];
+    if (b.n == WT_MAX || (lp && b.n > 0 && op.reserved != dtype)) {
+      const int rc = flush();
+      if (rc != WSIS_OK) return rc;
+    }
+    const bool fwd = op.kind == WSIS_OP_CONV;
+    dtype = op.reserved;
+    b.src[b.n] = (const float*)(fwd ? op.in[3] : op.in[1]);
+    b.dst[b.n] = base + off[i];
+    b.K[b.n] = op.K;
+    b.Cin[b.n] = op.Cin;
+    b.Cout[b.n] = op.Cout;
+    b.flip[b.n] = ((lp || !fwd) && (op.flags & WSIS_OPF_FLIP)) ? 1 : 0;
+    b.start[b.n + 1] = b.start[b.n] + op.K * ((op.Cin + WT_TILE - 1) / WT_TILE) * ((op.Cout + WT_TILE - 1) / WT_TILE);
+    ++b.n;
+  }
+  return flush();
+}
+
+// the side stream and worker of the weight gradients, then the 16-bit weights: cast from the fp32 masters in THIS call
+// (the pass follows every optimizer step) on the caller's stream.  Nothing is forked yet: an error leaves nothing to join
+int PassRun::start() {
+  side = (plan.dw_max > 0 && opt.dw_stream) ? side_stream_for(st) : nullptr;
+  if (side) side->next = 0;
+  use_worker = side != nullptr && opt.dw_thread && !opt.prof && !opt.capturing;
+  if (use_worker && hipGetDevice(&cur_dev) != hipSuccess) return fail(WSIS_ERR_HIP, "hipGetDevice failed");
+  dw_recs.resize((size_t)(opt.dw_defer() ? plan.n_dw : 0));
+  bn_unfused.assign(n, 0);
+  return launch_weight_batches<uint16_t>(ops, n, plan.lp_off, region(PassPlan::LP), st);
+}
+
+// The transposes (one launch, 28 us at the top of a forward pass) depend on the weights alone: they go to the library's
+// side stream behind an event of the caller's stream, and the caller's stream waits for them in front of the first op
+// that reads a transposed weight -- the 6-channel input convolution and its BatchNorm run meanwhile.  Not with the
+// resident deep-level launches of the EXPERIMENTAL build: a run of ops is issued as one launch there.
+int PassRun::fork_weight_transposes() {
+  bool any_wt = false;
+  for (int i = 0; i < n && !any_wt; ++i) any_wt = plan.wt_off[i] >= 0;
+  if (opt.wt_side && opt.dw_stream && !opt.capturing && any_wt && plan.wt_off[0] < 0 && !opt.prof &&
+      plan.bytes[PassPlan::DEEP] == 0)
+    wt_side = side_stream_for(st);
+  if (wt_side) {
+    hipError_t e = hipEventRecord(wt_side->wt_fork, st);
+    if (e == hipSuccess) e = hipStreamWaitEvent(wt_side->stream, wt_side->wt_fork, 0);
+    if (e != hipSuccess) return fail(WSIS_ERR_HIP, "weight-transpose fork failed: %s", hipGetErrorString(e));
+  }
+  int rc = launch_weight_batches<float>(ops, n, plan.wt_off, region(PassPlan::WT), wt_side ? wt_side->stream : st);
+  if (wt_side) {      // whatever the launches said: what reached the side stream is waited for (finish)
+    const hipError_t e = hipEventRecord(wt_side->wt_done, wt_side->stream);
+    wt_pending = e == hipSuccess;
+    if (!wt_pending && rc == WSIS_OK) rc = fail(WSIS_ERR_HIP, "weight-transpose event failed: %s", hipGetErrorString(e));
+  }
+  return rc;
+}
+
+int PassRun::await_transposes_before(int i) {
+  if (!wt_pending || plan.wt_off[i] < 0) return WSIS_OK;      // (the first reader of a transposed weight waits)
+  wt_pending = false;
+  const hipError_t e = hipStreamWaitEvent(st, wt_side->wt_done, 0);
+  return e == hipSuccess ? WSIS_OK : fail(WSIS_ERR_HIP, "weight-transpose join failed: %s", hipGetErrorString(e));
+}
+
+int PassRun::drain_worker() {      // every dW task pushed so far has been issued (and did it fail?)
+  if (!worker_busy) return WSIS_OK;
+  worker_busy = false;
+  std::string msg;
+  const int wrc = dw_worker().drain(&msg);
+  return wrc == WSIS_OK ? WSIS_OK : fail(wrc, "%s", msg.c_str());
+}
+
+// weight gradient of a CONV_BWD op: forked to the side stream behind everything enqueued so far on the caller's stream
+int PassRun::dw_issue(const wsis_op& op) {
+  void* dw_stream = stream;
+  char* my_ws = region(PassPlan::DW);
+  int64_t my_bytes = plan.dw_max;
+  DwRedRec* rec = nullptr;
+  if (opt.dw_defer() && dw_next < plan.n_dw) {
+    my_bytes = dw_ws_of(op);
+    my_ws += dw_off;
+    dw_off += my_bytes;
+    rec = &dw_recs[(size_t)dw_next++];
+  }
+  if (side) {   // dY is complete once everything enqueued so far on the caller's stream has run
+    hipEvent_t e = next_fork_event(side);
+    hipError_t he = e ? hipEventRecord(e, st) : hipErrorOutOfMemory;
+    if (he == hipSuccess && !use_worker) he = hipStreamWaitEvent(side->stream, e, 0);
+    if (he != hipSuccess) return fail(WSIS_ERR_HIP, "dW side-stream fork failed: %s", hipGetErrorString(he));
+    dw_stream = side->stream;
+    forked = true;
+    if (use_worker) {     // the wait and the launches come from the worker thread, in push order
+      DwTask t;
+      t.op = op;
+      t.ev = e;
+      t.dev = cur_dev;
+      t.side = side->stream;
+      t.ws = my_ws;
+      t.ws_bytes = my_bytes;
+      t.rec = rec;
+      dw_worker().push(t);
+      worker_busy = true;
+      return WSIS_OK;
+    }
+  }
+  return issue_dw(op, my_ws, my_bytes, dw_stream, rec);
+}
+
+// ONE launch finishes the deferred products issued since the last flush (behind them on their stream)
+int PassRun::dw_flush() {
+  if (dw_flushed == dw_next) return WSIS_OK;
+  const DwRedRec* recs = dw_recs.data() + dw_flushed;
+  const int cnt = dw_next - dw_flushed;
+  dw_flushed = dw_next;
+  if (side && use_worker) {
+    DwTask t;
+    t.ev = nullptr;
+    t.dev = cur_dev;
+    t.side = side->stream;
+    t.ws = nullptr;
+    t.ws_bytes = 0;
+    t.flush = recs;
+    t.flush_n = cnt;
+    dw_worker().push(t);
+    worker_busy = true;
+    return WSIS_OK;
+  }
+  return dw2_reduce_batch(recs, cnt, side ? side->stream : st);
+}
+
+// milestone: waiter_stream continues once everything issued so far -- on the caller's stream AND on the weight-gradient
+// side stream -- has run (gradient exchange of the finished part of the flat buffer while the rest of the pass executes)
+int PassRun::milestone() {
+  SideStream* ms = side ? side : side_stream_for(st);
+  int wrc = dw_flush();                         // the weight gradients up to here are FINAL behind their stream's event
+  if (wrc == WSIS_OK) wrc = drain_worker();     // the dW launches up to here are on the side stream before its event
+  if (wrc != WSIS_OK) return wrc;
+  hipError_t e = ms ? hipEventRecord(ms->mark_main, st) : hipErrorOutOfMemory;
+  if (e == hipSuccess) e = hipStreamWaitEvent(as_stream(waiter_stream), ms->mark_main, 0);
+  if (e == hipSuccess && forked) {
+    e = hipEventRecord(ms->mark_side, side->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(as_stream(waiter_stream), ms->mark_side, 0);
+  }
+  return e == hipSuccess ? WSIS_OK : fail(WSIS_ERR_HIP, "wsis_run_ops: milestone failed: %s", hipGetErrorString(e));
+}
+
+// The one exit of a pass that may have forked.  Whatever follows on the caller's stream (optimizer, gradient all-reduce,
+// the caller's error handling, the allocator handing the workspace to someone else) is ordered behind every launch the
+// pass put on the side stream: the weight gradients, and the weight transposes when an error ended the pass in front of
+// their first reader.  defer_join: a part of a pass leaves the weight-gradient join to a later part.
+int PassRun::finish(int first_err, bool defer_join) {
+  int wrc = first_err == WSIS_OK ? dw_flush() : WSIS_OK;      // (every part of a pass finishes its own products)
+  if (wrc != WSIS_OK && first_err == WSIS_OK) first_err = wrc;
+  wrc = drain_worker();
+  if (wrc != WSIS_OK && first_err == WSIS_OK) first_err = wrc;
+  if (wt_pending) {
+    wt_pending = false;
+    const hipError_t e = hipStreamWaitEvent(st, wt_side->wt_done, 0);
+    if (e != hipSuccess && first_err == WSIS_OK)
+      first_err = fail(WSIS_ERR_HIP, "weight-transpose join failed: %s", hipGetErrorString(e));
+  }
+  if (defer_join && first_err == WSIS_OK) {
+    if (forked) side->pending_join = true;
+    return WSIS_OK;
+  }
+  if (!forked && !side && opt.dw_stream) {      // a part without weight gradients of its own may owe an earlier part's join
+    SideStream* s2 = side_stream_for(st);
+    if (s2 && s2->pending_join) {
+      side = s2;
+      forked = true;
+    }
+  } else if (side && side->pending_join) {
+    forked = true;
+  }
+  if (forked) {
+    side->pending_join = false;
+    const hipError_t e1 = hipEventRecord(side->join, side->stream);
+    const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(st, side->join, 0) : e1;
+    if (e2 != hipSuccess && first_err == WSIS_OK)
+      return fail(WSIS_ERR_HIP, "side-stream join failed: %s", hipGetErrorString(e2));
+  }
+  return first_err;
+}
+
+// ---- one function per op kind.  Nothing here returns past finish(): a status goes back to the op loop
+inline int launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? WSIS_OK : fail(WSIS_ERR_HIP, "wsis_run_ops: launch failed: %s", hipGetErrorString(e));
+}
+inline int relu_of(const wsis_op& op) { return (op.flags & WSIS_OPF_RELU) ? 1 : 0; }
+inline int flip_of(const wsis_op& op) { return (op.flags & WSIS_OPF_FLIP) ? 1 : 0; }
+
+int issue_conv(PassRun& r, const wsis_op& op, int i) {
+  if (is_lp(op))      // 16-bit: X, residual and Y in op.reserved's dtype, weights cast at the top of the call
+    return wsis_spconv_fwd_lp_res(op.in[0], (const int32_t*)op.in[1], (const int32_t*)op.in[2], r.region(PassPlan::LP) + r.plan.lp_off[i],
+                                  0, (const float*)op.in[4], op.in[5], op.out[0], op.M_in, op.M_out, op.K, op.Cin,
+                                  op.Cout, op.reserved, r.ws, r.ws_bytes, r.stream);
+  if (op.flags & (WSIS_OPF_BN_IN | WSIS_OPF_STAT_FIN)) return issue_conv_fused_bn(r, op, i);
+  if (r.plan.wt_off[i] >= 0)
+    return wsis_spconv_fwd_t((const float*)op.in[0], (const int32_t*)op.in[1], (const int32_t*)op.in[2], r.wt_of(i), 0,
+                             (const float*)op.in[4], (const float*)op.in[5], (float*)op.out[0],
+                             (op.flags & WSIS_OPF_STATS) ? (float*)op.out[1] : nullptr, op.M_in, op.M_out, op.K, op.Cin,
+                             op.Cout, r.ws, r.ws_bytes, sync_slot(r.d_sync, i), r.stream);
+  if (op.flags & WSIS_OPF_STATS)
+    // the program was recorded for the kernel that writes BatchNorm partials; this launch cannot use it (input of 2 GiB
+    // or more, or WSIS_FWD2 changed between recording and running)
+    return fail(WSIS_ERR_ARG, "op %d: statistics requested from a convolution that is not on wsis_spconv_fwd_t", i);
+  return wsis_spconv_fwd((const float*)op.in[0], (const int32_t*)op.in[1], (const int32_t*)op.in[2], (const float*)op.in[3],
+                         (const float*)op.in[4], (const float*)op.in[5], (float*)op.out[0], op.M_in, op.M_out, op.K,
+                         op.Cin, op.Cout, r.ws, r.ws_bytes, r.stream);
+}
+
+// training: the statistics of x (out[1], out[2]) first
+int bn_training_stats(PassRun& r, const wsis_op& op, int i, bool* applied) {
+  const bool upd = (op.flags & WSIS_OPF_UPDATE_RUNNING) != 0;
+  float* rm = upd ? (float*)op.in[3] : nullptr;
+  float* rv = upd ? (float*)op.in[4] : nullptr;
+  if (!(op.flags & WSIS_OPF_STATS) || op.M_in <= 0)
+    return wsis_bn_stats((const float*)op.in[0], op.M_in, op.Cin, (float*)op.out[1], (float*)op.out[2], rm, rv,
+                         op.momentum, r.ws, r.ws_bytes, r.stream);
+  // the producers' epilogues left (sum, sum of squares) partials per 32-row slice: no pass over x
+  const int64_t n_part = (op.M_in + 31) / 32;
+  const int C0 = op.in[6] ? op.K : op.Cin;
+  if (!op.in[6] && op.out[0]) {     // one producer: statistics finish and apply pass in one launch (falls back by itself)
+    *applied = true;
+    return wsis_bn_stats_finalize_apply((const float*)op.in[5], n_part, op.M_in, op.Cin, (float*)op.out[1],
+                                        (float*)op.out[2], rm, rv, op.momentum, (const float*)op.in[0],
+                                        (const float*)op.in[1], (const float*)op.in[2], op.eps, relu_of(op),
+                                        (float*)op.out[0], r.ws, r.ws_bytes, sync_slot(r.d_sync, i), r.stream);
+  }
+  int rc = wsis_bn_stats_finalize((const float*)op.in[5], n_part, op.M_in, C0, (float*)op.out[1], (float*)op.out[2], rm,
+                                  rv, op.momentum, r.ws, r.ws_bytes, sync_slot(r.d_sync, i), r.stream);
+  if (rc == WSIS_OK && op.in[6])
+    rc = wsis_bn_stats_finalize((const float*)op.in[6], n_part, op.M_in, op.Cin - C0, (float*)op.out[1] + C0,
+                                (float*)op.out[2] + C0, rm ? rm + C0 : nullptr, rv ? rv + C0 : nullptr, op.momentum,
+                                r.ws, r.ws_bytes, sync_slot(r.d_sync, i), r.stream);
+  return rc;
+}
+
+int bn_relu_launches(PassRun& r, const wsis_op& op, int i) {
+  if (is_lp(op))      // evaluation form: the running statistics, 16-bit x, 16-bit (or fp32) y
+    return wsis_bn_apply_lp(op.in[0], (const float*)op.in[3], (const float*)op.in[4], (const float*)op.in[1],
+                            (const float*)op.in[2], op.eps, relu_of(op), op.out[0], (op.flags & WSIS_OPF_OUT_F32) ? 1 : 0,
+                            op.M_in, op.Cin, op.reserved, r.stream);
+  const bool training = (op.flags & WSIS_OPF_TRAINING) != 0;
+  if (training) {
+    bool applied = false;
+    const int rc = bn_training_stats(r, op, i, &applied);
+    if (rc != WSIS_OK || applied) return rc;
+  }
+  if (!op.out[0]) return WSIS_OK;      // statistics only: the consuming convolution applies the BatchNorm as it reads
+  return wsis_bn_apply((const float*)op.in[0], (const float*)(training ? op.out[1] : op.in[3]),
+                       (const float*)(training ? op.out[2] : op.in[4]), (const float*)op.in[1], (const float*)op.in[2],
+                       op.eps, relu_of(op), (float*)op.out[0], op.M_in, op.Cin, r.stream);
+}
+
+// bench.py's BatchNorm line (wsis_prof_records(2, ...)): one event pair around ALL launches of a BatchNorm op (the scope
+// does nothing unless the profiler is on)
+int issue_bn_relu(PassRun& r, const wsis_op& op, int i) {
+  ProfScope prof(2, r.st);
+  const int rc = bn_relu_launches(r, op, i);
+  prof.stop();
+  return rc;
+}
+
+int issue_cat(PassRun& r, const wsis_op& op, int) {
+  if (op.M_in <= 0) return WSIS_OK;
+  // a 16-bit [M, C] tensor with C even is an [M, C / 2] tensor of 4-byte words: the fp32 concatenation with halved
+  // channel counts copies every 16-bit value bit for bit (no kernel of its own)
+  wsis_op c = op;
+  if (is_lp(op)) {
+    c.Cin /= 2;
+    c.Cout /= 2;
+  }
+  if (vec4_ok(c, c.in[0], c.in[1], c.out[0]))
+    hipLaunchKernelGGL(cat_rows_kernel<4>, dim3(grid_for(c.M_in * (c.Cin + c.Cout) / 4, 256)), dim3(256), 0, r.st,
+                       (const float*)c.in[0], (const float*)c.in[1], (float*)c.out[0], c.M_in, c.Cin, c.Cout);
+  else
+    hipLaunchKernelGGL(cat_rows_kernel<1>, dim3(grid_for(c.M_in * (c.Cin + c.Cout), 256)), dim3(256), 0, r.st,
+                       (const float*)c.in[0], (const float*)c.in[1], (float*)c.out[0], c.M_in, c.Cin, c.Cout);
+  return launch_status();
+}
+
+int issue_cast_lp(PassRun& r, const wsis_op& op, int) {
+  const int64_t ne = op.M_in * op.Cin;
+  if (ne <= 0) return WSIS_OK;
+  const bool vec = ne % 4 == 0 && ((reinterpret_cast<uintptr_t>(op.in[0]) & 15) | (reinterpret_cast<uintptr_t>(op.out[0]) & 7)) == 0;
+  const int64_t items = vec ? ne / 4 : ne;
+  if (op.reserved == 0)
+    hipLaunchKernelGGL(cast_lp_kernel<__bf16>, dim3(grid_for(items, 256)), dim3(256), 0, r.st, (const float*)op.in[0],
+                       (__bf16*)op.out[0], ne, vec ? 1 : 0);
+  else
+    hipLaunchKernelGGL(cast_lp_kernel<_Float16>, dim3(grid_for(items, 256)), dim3(256), 0, r.st, (const float*)op.in[0],
+                       (_Float16*)op.out[0], ne, vec ? 1 : 0);
+  return launch_status();
+}
+
+int issue_split(PassRun& r, const wsis_op& op, int) {
+  if (op.M_in <= 0) return WSIS_OK;
+  if (vec4_ok(op, op.in[0], op.out[0], op.out[1]))
+    hipLaunchKernelGGL(split_rows_kernel<4>, dim3(grid_for(op.M_in * (op.Cin + op.Cout) / 4, 256)), dim3(256), 0, r.st,
+                       (const float*)op.in[0], (float*)op.out[0], (float*)op.out[1], op.M_in, op.Cin, op.Cout);
+  else
+    hipLaunchKernelGGL(split_rows_kernel<1>, dim3(grid_for(op.M_in * (op.Cin + op.Cout), 256)), dim3(256), 0, r.st,
+                       (const float*)op.in[0], (float*)op.out[0], (float*)op.out[1], op.M_in, op.Cin, op.Cout);
+  return launch_status();
+}
+
+int issue_add(PassRun& r, const wsis_op& op, int) {
+  if (op.M_in * op.Cin <= 0) return WSIS_OK;
+  hipLaunchKernelGGL(add_inplace_kernel, dim3(grid_for(op.M_in * op.Cin, 256)), dim3(256), 0, r.st, (float*)op.out[0],
+                     (const float*)op.in[0], op.M_in * op.Cin);
+  return launch_status();
+}
+
+// the dIn product of a CONV_BWD op (in: X, W, dY, nbr_f, order_f, nbr_b, order_b ; out: dX, dW)
+int issue_din(PassRun& r, const wsis_op& op, int i) {
+  const float* dY = (const float*)op.in[2];
+  const int32_t *nbr = (const int32_t*)op.in[5], *order = (const int32_t*)op.in[6];
+  float* dX = (float*)op.out[0];
+  const bool stats = (op.flags & WSIS_OPF_STATS) != 0;
+  if (r.plan.wt_off[i] >= 0) {
+    if (stats)
+      return fail(WSIS_ERR_ARG, "op %d: BatchNorm partials requested from a dIn pass that is not on wsis_spconv_fwd_t", i);
+    return wsis_spconv_fwd(dY, nbr, order, r.wt_of(i), nullptr, nullptr, dX, op.M_out, op.M_in, op.K, op.Cout, op.Cin, r.ws,
+                           r.ws_bytes, r.stream);
+  }
+  // (the weight [K, Cin, Cout] is the B^T operand of the dIn product as it stands)
+  const int j = stats ? paired_bn(r.ops, r.n, i) : -1;
+  if (stats && (j < 0 || !r.ops[j].in[7] || r.ops[j].M_in != op.M_in || r.ops[j].Cin != op.Cin))
+    return fail(WSIS_ERR_ARG, "op %d: no BatchNorm backward takes the partials of this dIn pass", i);
+  // few slices: the product is split into offset slabs and summed by a second kernel; the BatchNorm's own small-level
+  // reduction (one launch) is cheaper than a statistics variant of that sum
+  const bool unfused = stats && !r.opt.slab_bn_partials && wsis_spconv_fwd_t_slabs(op.M_in, op.K, op.Cout, op.Cin) > 1;
+  if (unfused) r.bn_unfused[j] = 1;
+  if (!stats || unfused)
+    return wsis_spconv_fwd_t(dY, nbr, order, (const float*)op.in[1], flip_of(op), nullptr, nullptr, dX, nullptr, op.M_out,
+                             op.M_in, op.K, op.Cout, op.Cin, r.ws, r.ws_bytes, sync_slot(r.d_sync, i), r.stream);
+  const wsis_op& bn = r.ops[j];
+  return wsis_spconv_fwd_t_bn(dY, nbr, order, (const float*)op.in[1], flip_of(op), dX, (float*)const_cast<void*>(bn.in[7]),
+                              (const float*)bn.in[0], (const float*)bn.in[2], (const float*)bn.in[3], (const float*)bn.in[4],
+                              (const float*)bn.in[5], bn.eps, relu_of(bn), op.M_out, op.M_in, op.K, op.Cout, op.Cin, r.ws,
+                              r.ws_bytes, sync_slot(r.d_sync, i), r.stream);
+}
+
+int issue_conv_bwd(PassRun& r, const wsis_op& op, int i) {
+  // The weight gradient needs X (saved by the forward pass) and dY -- complete once everything enqueued so far has run --
+  // but NOT this op's own dIn product: forked in front of it, it starts beside the dIn launch that reads the same dY
+  // instead of behind it, and the side stream runs one product further ahead all the way to the tail of the pass.
+  // WSIS_DW_EARLY=0: forked behind the dIn launch.
+  const bool early = r.opt.dw_early && op.out[1] && op.out[0] && r.side;
+  int rc = early ? r.dw_issue(op) : WSIS_OK;
+  if (rc == WSIS_OK && op.out[0]) rc = issue_din(r, op, i);
+  if (rc != WSIS_OK || !op.out[1] || early) return rc;
+  if (r.opt.dw_tail_main && r.side && dw_tail_on_main(r.ops, r.n, i))
+    // (never deferred: the batched slab sum runs on the side stream, these slabs are written on this one)
+    return issue_dw(op, r.ws, r.ws_bytes, r.stream, nullptr);
+  return r.dw_issue(op);
+}
+
+int issue_bn_relu_bwd(PassRun& r, const wsis_op& op, int i) {
+  ProfScope prof(2, r.st);      // (see issue_bn_relu)
+  int rc;
+  if ((op.flags & WSIS_OPF_STATS) && !r.bn_unfused[i]) {      // the producing dIn pass left the slice partials in in[7]
+    if (!op.in[7] || !(op.flags & WSIS_OPF_TRAINING))
+      rc = fail(WSIS_ERR_ARG, "op %d: BatchNorm backward from partials needs in[7] and training mode", i);
+    else
+      rc = wsis_bn_bwd_from_partials((const float*)op.in[7], (op.M_in + 31) / 32, (const float*)op.in[0],
+                                     (const float*)op.in[1], (const float*)op.in[2], (const float*)op.in[3],
+                                     (const float*)op.in[4], (const float*)op.in[5], op.eps, relu_of(op), (float*)op.out[0],
+                                     (float*)op.out[1], (float*)op.out[2], (const float*)op.in[6], op.M_in, op.Cin, r.ws,
+                                     r.ws_bytes, sync_slot(r.d_sync, i), r.stream);
+  } else {
+    rc = wsis_bn_bwd((const float*)op.in[0], (const float*)op.in[1], (const float*)op.in[2], (const float*)op.in[3],
+                     (const float*)op.in[4], (const float*)op.in[5], op.eps, relu_of(op),
+                     (op.flags & WSIS_OPF_TRAINING) ? 1 : 0, (float*)op.out[0], (float*)op.out[1], (float*)op.out[2],
+                     (const float*)op.in[6], op.M_in, op.Cin, r.ws, r.ws_bytes, r.stream);
+  }
+  prof.stop();
+  return rc;
+}
+
+int issue_op(PassRun& r, const wsis_op& op, int i) {
+  switch (op.kind) {
+    case WSIS_OP_CONV: return issue_conv(r, op, i);
+    case WSIS_OP_BN_RELU: return issue_bn_relu(r, op, i);
+    case WSIS_OP_CAT: return issue_cat(r, op, i);
+    case WSIS_OP_CAST_LP: return issue_cast_lp(r, op, i);
+    case WSIS_OP_SPLIT: return issue_split(r, op, i);
+    case WSIS_OP_ADD: return issue_add(r, op, i);
+    case WSIS_OP_CONV_BWD: return issue_conv_bwd(r, op, i);
+    case WSIS_OP_BN_RELU_BWD: return issue_bn_relu_bwd(r, op, i);
+    default: return fail(WSIS_ERR_ARG, "wsis_run_ops: unknown op kind");
+  }
+}
+
+int run_ops_impl(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_bytes, void* d_sync, void* stream, int32_t mark_op,
+                 void* waiter_stream, bool defer_join = false) {
+  WSIS_REQUIRE((ops || n == 0) && n >= 0, "bad op list");
+  WSIS_REQUIRE(mark_op < n && (mark_op < 0 || waiter_stream), "bad milestone");
+  PassRun r{ops, n, mark_op, d_sync, stream, waiter_stream, as_stream(stream)};
+  r.opt = read_pass_options(&r.st);
+  int err = plan_pass(ops, n, r.opt, r.plan);
+  if (err != WSIS_OK) return err;
+  WSIS_REQUIRE((n == 0 || ws_bytes >= r.plan.total) && (d_ws || n == 0), "workspace too small");
+  r.base = static_cast<char*>(d_ws);
+  r.ws = r.region(PassPlan::OP);
+  r.ws_bytes = ws_bytes - r.plan.at[PassPlan::OP];
+  err = r.start();
+  if (err != WSIS_OK) return err;      // (nothing forked yet; from here on finish() is the way out)
+  err = r.fork_weight_transposes();
+  for (int i = 0; i < n && err == WSIS_OK; ++i) {
+    err = r.await_transposes_before(i);
+    int next = i;
+    if (err == WSIS_OK) err = deep_issue_run(r, i, &next);      // (EXPERIMENTAL build: ops [i, next) as one launch)
+    if (err == WSIS_OK && next == i) err = issue_op(r, ops[i], i);
+    if (next > i) i = next - 1;
+    if (err == WSIS_OK && i == mark_op) err = r.milestone();
+  }
+  return r.finish(err, defer_join);
+}
 
 }  // namespace
 
@@ -752,35 +1404,31 @@ int wsis_warm_streams(void* stream) {
 
 int64_t wsis_run_ops_workspace_bytes(const wsis_op* ops, int32_t n) {
   if (!ops || n < 0) return -1;
-  int64_t need = ALIGN, wt = 0, dw = 0, dw_sum = 0;
-  const bool on = fwd2_enabled();
-  for (int i = 0; i < n; ++i) {
-    int64_t b = op_ws_bytes(ops[i], on);
-    if (b < 0) return -1;
-    if (dw_tail_on_main(ops, n, i)) b = std::max(b, dw_ws_of(ops[i]));      // (its slabs live in the op workspace)
-    if (b > need) need = b;
-    if (needs_wt(ops[i], on)) wt += wt_bytes_of(ops[i]);
-    if (is_lp_conv(ops[i])) wt += lp_wt_bytes_of(ops[i]);      // (the 16-bit weights, a region of their own)
-    if (ops[i].kind == WSIS_OP_CONV_BWD && ops[i].out[1]) {
-      const int64_t d = dw_ws_of(ops[i]);
-      if (d < 0) return -1;
-      if (d > dw) dw = d;
-      dw_sum += d;
-    }
+  PassPlan plan;
+  return plan_pass(ops, n, read_pass_options(nullptr), plan) == WSIS_OK ? plan.total : -1;
+}
+
+// diagnostic (not part of the ABI header): the plan a run of this op list would use under the present switches, so the
+// layout can be checked without a device.  out[0 .. 10): offset and size of the five regions in order, out[10]: the total,
+// then lp_off[0 .. n) and wt_off[0 .. n) (-1: the op has no weights there): 11 + 2 n words
+int wsis_debug_run_ops_layout(const wsis_op* ops, int32_t n, int64_t* out) {
+  WSIS_REQUIRE((ops || n == 0) && n >= 0 && out, "bad arguments");
+  PassPlan plan;
+  const int rc = plan_pass(ops, n, read_pass_options(nullptr), plan);
+  if (rc != WSIS_OK) return rc;
+  for (int k = 0; k < PassPlan::REGIONS; ++k) {
+    out[2 * k] = plan.at[k];
+    out[2 * k + 1] = plan.bytes[k];
   }
-  // (deferred slab sums: every product keeps its slabs until the batched launch; the switch is read per pass -- a pass
-  // whose workspace was sized with it off and that runs with it on fails its own size check)
-  const char* be = getenv("WSIS_DW_BATCH_REDUCE");
-  const bool batch = be && atoi(be) != 0;
-  return wt + (batch ? std::max(dw, dw_sum) : dw) + need + deep_ws_bytes(ops, n, on) + ALIGN;
+  out[10] = plan.total;
+  std::copy(plan.lp_off.begin(), plan.lp_off.end(), out + 11);
+  std::copy(plan.wt_off.begin(), plan.wt_off.end(), out + 11 + n);
+  return WSIS_OK;
 }
 
 int wsis_run_ops(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_bytes, void* d_sync, void* stream) {
   return wsis_run_ops_marked(ops, n, d_ws, ws_bytes, d_sync, stream, -1, nullptr);
 }
-
-static int run_ops_impl(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_bytes, void* d_sync, void* stream,
-                        int32_t mark_op, void* waiter_stream, bool defer_join = false);
 
 // A pass issued in PARTS (the host does something between two parts: the statistics exchange of a SyncBatchNorm layer,
 // model/unet_native.py): parts with last == 0 leave the weight-gradient side stream un-joined, the part with last != 0
@@ -862,636 +1510,6 @@ int wsis_run_ops_marked(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_by
   }
   return WSIS_OK;
 #endif
-}
-
-static int run_ops_impl(const wsis_op* ops, int32_t n, void* d_ws, int64_t ws_bytes, void* d_sync, void* stream,
-                        int32_t mark_op, void* waiter_stream, bool defer_join) {
-  WSIS_REQUIRE((ops || n == 0) && n >= 0, "bad op list");
-  WSIS_REQUIRE(mark_op < n && (mark_op < 0 || waiter_stream), "bad milestone");
-  for (int i = 0; i < n; ++i) {
-    const char* why = lp_refusal(ops[i]);
-    if (why) return fail(WSIS_ERR_ARG, "wsis_run_ops: op %d: %s", i, why);
-  }
-  WSIS_REQUIRE((n == 0 || ws_bytes >= wsis_run_ops_workspace_bytes(ops, n)) && (d_ws || n == 0), "workspace too small");
-  hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(d_ws);
-  // ---- the 16-bit B^T weights of the pass's 16-bit convolutions, cast from the fp32 masters in THIS call (the pass
-  // follows every optimizer step), WT_MAX layers of one dtype per launch, on the caller's stream and before any fork
-  // below: an error here leaves nothing to join
-  std::vector<int64_t> lp_off(n, -1);
-  int64_t lp_total = 0;
-  {
-    WtBatch b;
-    b.n = 0;
-    b.start[0] = 0;
-    int dtype = 0;
-    auto flush = [&]() -> int {
-      if (b.n == 0) return WSIS_OK;
-      if (dtype == 0)
-        hipLaunchKernelGGL(weight_transpose_batch_kernel<__bf16>, dim3(b.start[b.n]), dim3(256), 0, st, b);
-      else
-        hipLaunchKernelGGL(weight_transpose_batch_kernel<_Float16>, dim3(b.start[b.n]), dim3(256), 0, st, b);
-      WSIS_LAUNCH_CHECK();
-      b.n = 0;
-      return WSIS_OK;
-    };
-    for (int i = 0; i < n; ++i) {
-      const wsis_op& op = ops[i];
-      if (!is_lp_conv(op)) continue;
-      if (b.n == WT_MAX || (b.n > 0 && op.reserved != dtype)) {
-        const int rc = flush();
-        if (rc != WSIS_OK) return rc;
-      }
-      dtype = op.reserved;
-      lp_off[i] = lp_total;
-      b.src[b.n] = (const float*)op.in[3];
-      b.dst[b.n] = ws + lp_total;
-      b.K[b.n] = op.K;
-      b.Cin[b.n] = op.Cin;
-      b.Cout[b.n] = op.Cout;
-      b.flip[b.n] = (op.flags & WSIS_OPF_FLIP) ? 1 : 0;
-      b.start[b.n + 1] = b.start[b.n] + op.K * ((op.Cin + WT_TILE - 1) / WT_TILE) * ((op.Cout + WT_TILE - 1) / WT_TILE);
-      ++b.n;
-      lp_total += lp_wt_bytes_of(op);
-    }
-    const int rc = flush();
-    if (rc != WSIS_OK) return rc;
-  }
-  char* const lp_base = ws;
-  ws += lp_total;
-  ws_bytes -= lp_total;
-  char* const wt_base = ws;
-  // ---- all transposed weights of the pass, WT_MAX layers per launch; wt_off[i] = offset of op i's W^T
-  const bool on = fwd2_enabled();
-  std::vector<int64_t> wt_off(n, -1);
-  int64_t wt_total = 0;
-  // The transposes (one launch, 28 us at the top of a forward pass) depend on the weights alone: they go to the library's
-  // side stream behind an event of the caller's stream, and the caller's stream waits for them in front of the first op
-  // that reads a transposed weight -- the 6-channel input convolution and its BatchNorm run meanwhile.
-  // WSIS_WT_SIDE=0 (read per pass): on the caller's stream as before.
-  SideStream* wt_side = nullptr;
-  bool wt_pending = false;
-  {
-    const char* we = getenv("WSIS_WT_SIDE");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool cap = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    bool any_wt = false, first_needs = n > 0 && needs_wt(ops[0], on);
-    for (int i = 0; i < n && !any_wt; ++i) any_wt = needs_wt(ops[i], on);
-    // (not with the resident deep-level launches of the EXPERIMENTAL build: a run of ops is issued as one launch there)
-    if ((we ? atoi(we) != 0 : true) && dw_stream_enabled() && !cap && any_wt && !first_needs && !g_prof_on &&
-        deep_ws_bytes(ops, n, on) == 0)
-      wt_side = side_stream_for(st);
-    if (wt_side) {
-      hipError_t e = hipEventRecord(wt_side->wt_fork, st);
-      if (e == hipSuccess) e = hipStreamWaitEvent(wt_side->stream, wt_side->wt_fork, 0);
-      if (e != hipSuccess) return fail(WSIS_ERR_HIP, "weight-transpose fork failed: %s", hipGetErrorString(e));
-    }
-  }
-  hipStream_t wt_st = wt_side ? wt_side->stream : st;
-  {
-    WtBatch b;
-    b.n = 0;
-    b.start[0] = 0;
-    auto flush = [&]() -> int {
-      if (b.n == 0) return WSIS_OK;
-      hipLaunchKernelGGL(weight_transpose_batch_kernel<float>, dim3(b.start[b.n]), dim3(256), 0, wt_st, b);
-      WSIS_LAUNCH_CHECK();
-      b.n = 0;
-      return WSIS_OK;
-    };
-    for (int i = 0; i < n; ++i) {
-      const wsis_op& op = ops[i];
-      if (!needs_wt(op, on)) continue;
-      const bool fwd = op.kind == WSIS_OP_CONV;
-      const void* wsrc = fwd ? op.in[3] : op.in[1];
-      WSIS_REQUIRE(wsrc, "convolution without weights");
-      wt_off[i] = wt_total;
-      b.src[b.n] = (const float*)wsrc;
-      b.dst[b.n] = reinterpret_cast<float*>(ws + wt_total);
-      b.K[b.n] = op.K;
-      b.Cin[b.n] = op.Cin;
-      b.Cout[b.n] = op.Cout;
-      b.flip[b.n] = (!fwd && (op.flags & WSIS_OPF_FLIP)) ? 1 : 0;
-      b.start[b.n + 1] = b.start[b.n] + op.K * ((op.Cin + WT_TILE - 1) / WT_TILE) * ((op.Cout + WT_TILE - 1) / WT_TILE);
-      ++b.n;
-      wt_total += wt_bytes_of(op);
-      if (b.n == WT_MAX) {
-        const int rc = flush();
-        if (rc != WSIS_OK) return rc;
-      }
-    }
-    const int rc = flush();
-    if (rc != WSIS_OK) return rc;
-    if (wt_side) {
-      const hipError_t e = hipEventRecord(wt_side->wt_done, wt_side->stream);
-      if (e != hipSuccess) return fail(WSIS_ERR_HIP, "weight-transpose event failed: %s", hipGetErrorString(e));
-      wt_pending = true;
-    }
-  }
-  ws += wt_total;
-  ws_bytes -= wt_total;
-  // dW region (shared by the dW launches, which are ordered among themselves on one stream)
-  // ... or, with deferred slab sums, one region per product: its slabs live until the batched launch that sums them
-  const bool dw_defer = dw_batch_reduce_enabled();
-  const bool tail_main = dw_tail_main_enabled();
-  // (measured in-process: 7.69 -> 7.50 ms at one scene per step, 11.70 -> 11.50 at two, 20.11 -> 20.22 at four -- with a
-  // batch that fills the GPU the early product takes from the dIn launch beside it what it gains at the tail; default:
-  // by the batch hint, below WSIS_DW_EARLY_ROWS active voxels)
-  const char* early_env = getenv("WSIS_DW_EARLY");
-  const char* early_rows_env = getenv("WSIS_DW_EARLY_ROWS");
-  const int64_t early_rows = early_rows_env ? atoll(early_rows_env) : 500000;
-  const bool dw_early = early_env ? atoi(early_env) != 0 : dw2_batch_rows() < early_rows;
-  int64_t dw_bytes = 0, dw_sum = 0;
-  int n_dw = 0;
-  for (int i = 0; i < n; ++i)
-    if (ops[i].kind == WSIS_OP_CONV_BWD && ops[i].out[1]) {
-      const int64_t d = dw_ws_of(ops[i]);
-      if (d > dw_bytes) dw_bytes = d;
-      dw_sum += d;
-      ++n_dw;
-    }
-  char* const dw_ws = ws;
-  ws += dw_defer ? dw_sum : dw_bytes;
-  ws_bytes -= dw_defer ? dw_sum : dw_bytes;
-  if (ws_bytes < 0) return fail(WSIS_ERR_ARG, "wsis_run_ops: workspace too small for the weight-gradient slabs");
-  // record slots of the pass's deferred products (stable addresses: the worker thread fills them) and what has been
-  // flushed so far; the vector outlives every task that points into it (drained before this function returns)
-  std::vector<DwRedRec> dw_recs((size_t)(dw_defer ? n_dw : 0));
-  int dw_next = 0, dw_flushed = 0;
-  int64_t dw_off = 0;
-  // resident deep-level launches (deep.hip): phase table + private slab regions of the largest run
-  const int64_t deep_bytes = deep_ws_bytes(ops, n, on);
-  char* const deep_ws = ws;
-  (void)deep_ws;
-  ws += deep_bytes;
-  ws_bytes -= deep_bytes;
-  SideStream* side = (dw_bytes > 0 && dw_stream_enabled()) ? side_stream_for(st) : nullptr;
-  if (side) side->next = 0;
-  // the side-stream calls of the pass from a second host thread (not under stream capture, not while the profiler's
-  // event lists are being filled: those are single-threaded)
-  hipStreamCaptureStatus cap_state = hipStreamCaptureStatusNone;
-  const bool capturing = hipStreamIsCapturing(st, &cap_state) != hipSuccess || cap_state != hipStreamCaptureStatusNone;
-  const bool use_worker = side != nullptr && dw_thread_enabled() && !g_prof_on && !capturing;
-  int cur_dev = 0;
-  if (use_worker && hipGetDevice(&cur_dev) != hipSuccess) return fail(WSIS_ERR_HIP, "hipGetDevice failed");
-  bool worker_busy = false;
-  auto drain_worker = [&]() -> int {      // every dW task pushed so far has been issued (and did it fail?)
-    if (!worker_busy) return WSIS_OK;
-    worker_busy = false;
-    std::string msg;
-    const int wrc = dw_worker().drain(&msg);
-    return wrc == WSIS_OK ? WSIS_OK : fail(wrc, "%s", msg.c_str());
-  };
-  // inside the op loop nothing returns directly: an error after the fork still has to reach the join below
-#define RUN_LAUNCH_CHECK()                                                                              \
-  do {                                                                                                  \
-    const hipError_t le_ = hipGetLastError();                                                           \
-    if (le_ != hipSuccess) rc = fail(WSIS_ERR_HIP, "wsis_run_ops: launch failed: %s", hipGetErrorString(le_)); \
-  } while (0)
-  bool forked = false;
-  int first_err = WSIS_OK;
-  // weight gradient of a CONV_BWD op: forked to the side stream behind everything enqueued so far on the caller's stream
-  auto dw_issue = [&](const wsis_op& op) -> int {
-    void* dw_stream = stream;
-    char* my_ws = dw_ws;
-    int64_t my_bytes = dw_bytes;
-    DwRedRec* rec = nullptr;
-    if (dw_defer && dw_next < n_dw) {
-      my_bytes = dw_ws_of(op);
-      my_ws = dw_ws + dw_off;
-      dw_off += my_bytes;
-      rec = &dw_recs[(size_t)dw_next++];
-    }
-    if (side) {   // dY is complete once everything enqueued so far on the caller's stream has run
-      hipEvent_t e = next_fork_event(side);
-      hipError_t he = e ? hipEventRecord(e, st) : hipErrorOutOfMemory;
-      if (he == hipSuccess && !use_worker) he = hipStreamWaitEvent(side->stream, e, 0);
-      if (he != hipSuccess) return fail(WSIS_ERR_HIP, "dW side-stream fork failed: %s", hipGetErrorString(he));
-      dw_stream = side->stream;
-      forked = true;
-      if (use_worker) {     // the wait and the launches come from the worker thread, in push order
-        DwTask t;
-        t.op = op;
-        t.ev = e;
-        t.dev = cur_dev;
-        t.side = side->stream;
-        t.ws = my_ws;
-        t.ws_bytes = my_bytes;
-        t.rec = rec;
-        dw_worker().push(t);
-        worker_busy = true;
-        return WSIS_OK;
-      }
-    }
-    return issue_dw(op, my_ws, my_bytes, dw_stream, rec);
-  };
-  // ONE launch finishes the deferred products issued since the last flush (behind them on their stream)
-  auto dw_flush = [&]() -> int {
-    if (!dw_defer || dw_flushed == dw_next) return WSIS_OK;
-    const DwRedRec* recs = dw_recs.data() + dw_flushed;
-    const int cnt = dw_next - dw_flushed;
-    dw_flushed = dw_next;
-    if (side && use_worker) {
-      DwTask t;
-      t.ev = nullptr;
-      t.dev = cur_dev;
-      t.side = side->stream;
-      t.ws = nullptr;
-      t.ws_bytes = 0;
-      t.flush = recs;
-      t.flush_n = cnt;
-      dw_worker().push(t);
-      worker_busy = true;
-      return WSIS_OK;
-    }
-    return dw2_reduce_batch(recs, cnt, side ? side->stream : st);
-  };
-#if WSIS_EXPERIMENTAL
-  const bool deep_on = deep_bytes > 0 && d_sync != nullptr && !capturing;
-  std::vector<DeepOp> deep_tab;
-  std::vector<std::pair<int, std::pair<int, int>>> deep_convs;
-#endif
-  const char* slab_bn_env = getenv("WSIS_SLAB_BN_PARTIALS");      // one-shot path: slab-split dIn products write the
-  const bool slab_bn_partials = slab_bn_env && atoi(slab_bn_env) != 0;   // BatchNorm partials too (the resident kernel's form)
-  std::vector<char> bn_unfused(n, 0);     // BatchNorm backward ops whose dIn pass did not write partials this run
-  for (int i = 0; i < n; ++i) {
-    int rc = WSIS_OK;
-    if (wt_pending && wt_off[i] >= 0) {      // the first reader of a transposed weight
-      wt_pending = false;
-      const hipError_t e = hipStreamWaitEvent(st, wt_side->wt_done, 0);
-      if (e != hipSuccess) {
-        first_err = fail(WSIS_ERR_HIP, "weight-transpose join failed: %s", hipGetErrorString(e));
-        break;
-      }
-    }
-#if WSIS_EXPERIMENTAL
-    if (deep_on && deep_op_ok(ops, n, i, on)) {
-      const int i1 = deep_run_end(ops, n, i, mark_op >= i ? mark_op : -1, on);
-      if (i1 - i >= kDeepMinOps) {
-        // ---- ops [i, i1) as ONE resident launch; their weight gradients follow on the side stream
-        char* slab = deep_ws + deep_table_bytes(i1 - i);
-        rc = deep_build(ops, n, i, i1, wt_base, wt_off, slab, g_prof_on, deep_tab, deep_convs);
-        unsigned long long* d_stamps = nullptr;
-        if (rc == WSIS_OK && g_prof_on && !deep_tab.empty()) {
-          if (hipMalloc((void**)&d_stamps, (deep_tab.size() + 1) * sizeof(unsigned long long)) != hipSuccess)
-            rc = fail(WSIS_ERR_HIP, "deep: stamp buffer allocation failed");
-          else
-            g_prof_bufs.push_back(d_stamps);
-        }
-        if (rc == WSIS_OK)
-          rc = deep_launch(deep_tab.data(), (int)deep_tab.size(), deep_ws, deep_sync_slot(d_sync), d_stamps, st);
-        if (rc == WSIS_OK && d_stamps) {
-          if (g_deep_log.size() > 64) g_deep_log.clear();
-          g_deep_log.push_back({deep_tab, d_stamps});
-        }
-        if (rc == WSIS_OK && d_stamps)
-          for (const auto& cs : deep_convs) {
-            ProfRec r{};
-            r.d_stamps = d_stamps;
-            r.s0 = cs.second.first;
-            r.sm = cs.second.first + 1;
-            r.s1 = cs.second.second;
-            g_prof[0].push_back(r);
-          }
-        for (int k = i; k < i1 && rc == WSIS_OK; ++k)
-          if (ops[k].kind == WSIS_OP_CONV_BWD && ops[k].out[1]) rc = dw_issue(ops[k]);
-        if (rc != WSIS_OK) {
-          first_err = rc;
-          break;
-        }
-        i = i1 - 1;
-        goto op_done;
-      }
-    }
-#endif
-    {
-    const wsis_op& op = ops[i];
-    // bench.py's BatchNorm line (wsis_prof_records(2, ...)): one event pair around ALL launches of a BatchNorm op
-    const bool is_bn = op.kind == WSIS_OP_BN_RELU || op.kind == WSIS_OP_BN_RELU_BWD;
-    std::optional<ProfScope> bn_prof;
-    if (is_bn && g_prof_on) bn_prof.emplace(2, st);
-    switch (op.kind) {
-      case WSIS_OP_CONV:
-        if (is_lp(op)) {      // 16-bit: X, residual and Y in op.reserved's dtype, weights cast at the top of the call
-          rc = wsis_spconv_fwd_lp_res(op.in[0], (const int32_t*)op.in[1], (const int32_t*)op.in[2], lp_base + lp_off[i],
-                                      0, (const float*)op.in[4], op.in[5], op.out[0], op.M_in, op.M_out, op.K, op.Cin,
-                                      op.Cout, op.reserved, ws, ws_bytes, stream);
-          break;
-        }
-        if (op.flags & (WSIS_OPF_BN_IN | WSIS_OPF_STAT_FIN)) {
-#if !WSIS_EXPERIMENTAL
-          rc = fail(WSIS_ERR_ARG, "op %d: the fused BatchNorm forms of the convolution are in the EXPERIMENTAL build only", i);
-          break;
-#else
-          if (wt_off[i] < 0) {
-            rc = fail(WSIS_ERR_ARG, "op %d: fused BatchNorm requested from a convolution that is not on wsis_spconv_fwd_t", i);
-            break;
-          }
-          wsis_bn_in bi;
-          bi.mean = (const float*)op.in[6];
-          bi.var = (const float*)op.in[7];
-          bi.gamma = (const float*)op.in[8];
-          bi.beta = (const float*)op.in[9];
-          bi.eps = op.eps;
-          bi.relu = (op.flags & WSIS_OPF_RELU) ? 1 : 0;
-          wsis_stat_target tg[2];
-          int nt = 0;
-          if (op.flags & WSIS_OPF_STAT_FIN) {
-            tg[0].mean = (float*)op.out[2];
-            tg[0].var = (float*)op.out[3];
-            tg[0].running_mean = (float*)const_cast<void*>(op.in[10]);
-            tg[0].running_var = (float*)const_cast<void*>(op.in[11]);
-            tg[0].momentum = op.momentum;
-            tg[0].reserved = 0;
-            nt = 1;
-            if (op.out[4]) {
-              tg[1].mean = (float*)op.out[4];
-              tg[1].var = (float*)op.out[5];
-              tg[1].running_mean = (float*)op.out[6];
-              tg[1].running_var = (float*)op.out[7];
-              tg[1].momentum = op.momentum2;
-              tg[1].reserved = 0;
-              nt = 2;
-            }
-          }
-          rc = wsis_spconv_fwd_f((const float*)op.in[0], (op.flags & WSIS_OPF_BN_IN) ? &bi : nullptr, (const int32_t*)op.in[1],
-                                 (const int32_t*)op.in[2], reinterpret_cast<const float*>(wt_base + wt_off[i]), 0,
-                                 (const float*)op.in[4], (const float*)op.in[5], (float*)op.out[0],
-                                 (op.flags & WSIS_OPF_STATS) ? (float*)op.out[1] : nullptr, tg, nt, op.M_in, op.M_out, op.K,
-                                 op.Cin, op.Cout, ws, ws_bytes, sync_slot(d_sync, i), stream);
-          break;
-#endif
-        }
-        if (wt_off[i] >= 0)
-          rc = wsis_spconv_fwd_t((const float*)op.in[0], (const int32_t*)op.in[1], (const int32_t*)op.in[2],
-                                 reinterpret_cast<const float*>(wt_base + wt_off[i]), 0, (const float*)op.in[4],
-                                 (const float*)op.in[5], (float*)op.out[0],
-                                 (op.flags & WSIS_OPF_STATS) ? (float*)op.out[1] : nullptr, op.M_in, op.M_out, op.K,
-                                 op.Cin, op.Cout, ws, ws_bytes, sync_slot(d_sync, i), stream);
-        else if (op.flags & WSIS_OPF_STATS)
-          // the program was recorded for the kernel that writes BatchNorm partials; this launch cannot use it (input
-          // of 2 GiB or more, or WSIS_FWD2 changed between recording and running)
-          rc = fail(WSIS_ERR_ARG, "op %d: statistics requested from a convolution that is not on wsis_spconv_fwd_t", i);
-        else
-          rc = wsis_spconv_fwd((const float*)op.in[0], (const int32_t*)op.in[1], (const int32_t*)op.in[2],
-                               (const float*)op.in[3], (const float*)op.in[4], (const float*)op.in[5],
-                               (float*)op.out[0], op.M_in, op.M_out, op.K, op.Cin, op.Cout, ws, ws_bytes, stream);
-        break;
-      case WSIS_OP_BN_RELU: {
-        if (is_lp(op)) {      // evaluation form: the running statistics, 16-bit x, 16-bit (or fp32) y
-          rc = wsis_bn_apply_lp(op.in[0], (const float*)op.in[3], (const float*)op.in[4], (const float*)op.in[1],
-                                (const float*)op.in[2], op.eps, (op.flags & WSIS_OPF_RELU) ? 1 : 0, op.out[0],
-                                (op.flags & WSIS_OPF_OUT_F32) ? 1 : 0, op.M_in, op.Cin, op.reserved, stream);
-          break;
-        }
-        const float* mean = (const float*)op.out[1];
-        const float* var = (const float*)op.out[2];
-        if (op.flags & WSIS_OPF_TRAINING) {
-          const bool upd = (op.flags & WSIS_OPF_UPDATE_RUNNING) != 0;
-          float* rm = upd ? (float*)op.in[3] : nullptr;
-          float* rv = upd ? (float*)op.in[4] : nullptr;
-          if ((op.flags & WSIS_OPF_STATS) && op.M_in > 0) {
-            // the producers' epilogues left (sum, sum of squares) partials per 32-row slice: no pass over x
-            const int64_t n_part = (op.M_in + 31) / 32;
-            const int C0 = op.in[6] ? op.K : op.Cin;
-            if (!op.in[6] && op.out[0]) {     // one producer: statistics finish and apply pass in one launch (falls back by itself)
-              rc = wsis_bn_stats_finalize_apply((const float*)op.in[5], n_part, op.M_in, op.Cin, (float*)op.out[1],
-                                                (float*)op.out[2], rm, rv, op.momentum, (const float*)op.in[0],
-                                                (const float*)op.in[1], (const float*)op.in[2], op.eps,
-                                                (op.flags & WSIS_OPF_RELU) ? 1 : 0, (float*)op.out[0], ws, ws_bytes,
-                                                sync_slot(d_sync, i), stream);
-              break;
-            }
-            rc = wsis_bn_stats_finalize((const float*)op.in[5], n_part, op.M_in, C0, (float*)op.out[1],
-                                        (float*)op.out[2], rm, rv, op.momentum, ws, ws_bytes, sync_slot(d_sync, i), stream);
-            if (rc == WSIS_OK && op.in[6])
-              rc = wsis_bn_stats_finalize((const float*)op.in[6], n_part, op.M_in, op.Cin - C0, (float*)op.out[1] + C0,
-                                          (float*)op.out[2] + C0, rm ? rm + C0 : nullptr, rv ? rv + C0 : nullptr,
-                                          op.momentum, ws, ws_bytes, sync_slot(d_sync, i), stream);
-          } else {
-            rc = wsis_bn_stats((const float*)op.in[0], op.M_in, op.Cin, (float*)op.out[1], (float*)op.out[2], rm, rv,
-                               op.momentum, ws, ws_bytes, stream);
-          }
-          if (rc != WSIS_OK) break;
-        } else {
-          mean = (const float*)op.in[3];
-          var = (const float*)op.in[4];
-        }
-        if (!op.out[0]) break;      // statistics only: the consuming convolution applies the BatchNorm as it reads
-        rc = wsis_bn_apply((const float*)op.in[0], mean, var, (const float*)op.in[1], (const float*)op.in[2], op.eps,
-                           (op.flags & WSIS_OPF_RELU) ? 1 : 0, (float*)op.out[0], op.M_in, op.Cin, stream);
-        break;
-      }
-      case WSIS_OP_CAT:
-        if (op.M_in > 0) {
-          // a 16-bit [M, C] tensor with C even is an [M, C / 2] tensor of 4-byte words: the fp32 concatenation with
-          // halved channel counts copies every 16-bit value bit for bit (no kernel of its own)
-          wsis_op c = op;
-          if (is_lp(op)) {
-            c.Cin /= 2;
-            c.Cout /= 2;
-          }
-          if (vec4_ok(c, c.in[0], c.in[1], c.out[0]))
-            hipLaunchKernelGGL(cat_rows_kernel<4>, dim3(grid_for(c.M_in * (c.Cin + c.Cout) / 4, 256)), dim3(256), 0,
-                               st, (const float*)c.in[0], (const float*)c.in[1], (float*)c.out[0], c.M_in, c.Cin,
-                               c.Cout);
-          else
-            hipLaunchKernelGGL(cat_rows_kernel<1>, dim3(grid_for(c.M_in * (c.Cin + c.Cout), 256)), dim3(256), 0, st,
-                               (const float*)c.in[0], (const float*)c.in[1], (float*)c.out[0], c.M_in, c.Cin,
-                               c.Cout);
-          RUN_LAUNCH_CHECK();
-        }
-        break;
-      case WSIS_OP_CAST_LP: {
-        const int64_t ne = op.M_in * op.Cin;
-        if (ne > 0) {
-          const bool vec = ne % 4 == 0 && ((reinterpret_cast<uintptr_t>(op.in[0]) & 15) | (reinterpret_cast<uintptr_t>(op.out[0]) & 7)) == 0;
-          const int64_t items = vec ? ne / 4 : ne;
-          if (op.reserved == 0)
-            hipLaunchKernelGGL(cast_lp_kernel<__bf16>, dim3(grid_for(items, 256)), dim3(256), 0, st,
-                               (const float*)op.in[0], (__bf16*)op.out[0], ne, vec ? 1 : 0);
-          else
-            hipLaunchKernelGGL(cast_lp_kernel<_Float16>, dim3(grid_for(items, 256)), dim3(256), 0, st,
-                               (const float*)op.in[0], (_Float16*)op.out[0], ne, vec ? 1 : 0);
-          RUN_LAUNCH_CHECK();
-        }
-        break;
-      }
-      case WSIS_OP_SPLIT:
-        if (op.M_in > 0) {
-          if (vec4_ok(op, op.in[0], op.out[0], op.out[1]))
-            hipLaunchKernelGGL(split_rows_kernel<4>, dim3(grid_for(op.M_in * (op.Cin + op.Cout) / 4, 256)), dim3(256),
-                               0, st, (const float*)op.in[0], (float*)op.out[0], (float*)op.out[1], op.M_in, op.Cin,
-                               op.Cout);
-          else
-            hipLaunchKernelGGL(split_rows_kernel<1>, dim3(grid_for(op.M_in * (op.Cin + op.Cout), 256)), dim3(256), 0, st,
-                               (const float*)op.in[0], (float*)op.out[0], (float*)op.out[1], op.M_in, op.Cin, op.Cout);
-          RUN_LAUNCH_CHECK();
-        }
-        break;
-      case WSIS_OP_ADD:
-        if (op.M_in * op.Cin > 0) {
-          hipLaunchKernelGGL(add_inplace_kernel, dim3(grid_for(op.M_in * op.Cin, 256)), dim3(256), 0, st,
-                             (float*)op.out[0], (const float*)op.in[0], op.M_in * op.Cin);
-          RUN_LAUNCH_CHECK();
-        }
-        break;
-      case WSIS_OP_CONV_BWD: {
-        // in: X, W, dY, nbr_f, order_f, nbr_b, order_b ; out: dX (optional), dW (optional)
-        char* rest = ws;
-        const int64_t rest_bytes = ws_bytes;
-        // The weight gradient needs X (saved by the forward pass) and dY -- complete once everything enqueued so far has
-        // run -- but NOT this op's own dIn product: forked in front of it (round 6), it starts beside the dIn launch that
-        // reads the same dY instead of behind it, and the side stream runs one product further ahead all the way to the
-        // tail of the pass.  WSIS_DW_EARLY=0 (read per pass): forked behind the dIn launch as before.
-        bool dw_forked = false;
-        if (dw_early && op.out[1] && op.out[0] && side) {
-          rc = dw_issue(op);
-          dw_forked = true;
-          if (rc != WSIS_OK) break;
-        }
-        if (op.out[0]) {
-          if (wt_off[i] >= 0 && (op.flags & WSIS_OPF_STATS)) {
-            rc = fail(WSIS_ERR_ARG, "op %d: BatchNorm partials requested from a dIn pass that is not on wsis_spconv_fwd_t", i);
-            break;
-          }
-          if (wt_off[i] >= 0) {
-            const float* WT = reinterpret_cast<const float*>(wt_base + wt_off[i]);
-            rc = wsis_spconv_fwd((const float*)op.in[2], (const int32_t*)op.in[5], (const int32_t*)op.in[6], WT, nullptr,
-                                 nullptr, (float*)op.out[0], op.M_out, op.M_in, op.K, op.Cout, op.Cin, rest, rest_bytes,
-                                 stream);
-          } else if (op.flags & WSIS_OPF_STATS) {
-            // dX is the dy of a BatchNorm backward a few ops on (WSIS_OP_BN_RELU_BWD with in[1] == this dX, flagged
-            // too): the epilogue also makes that op's reduction, into its in[7]
-            const wsis_op* bn = nullptr;
-            for (int j = i + 1; j < n && j <= i + 4 && !bn; ++j)
-              if (ops[j].kind == WSIS_OP_BN_RELU_BWD && ops[j].in[1] == op.out[0] && (ops[j].flags & WSIS_OPF_STATS))
-                bn = &ops[j];
-            if (!bn || !bn->in[7] || bn->M_in != op.M_in || bn->Cin != op.Cin) {
-              rc = fail(WSIS_ERR_ARG, "op %d: no BatchNorm backward takes the partials of this dIn pass", i);
-              break;
-            }
-            if (!slab_bn_partials && wsis_spconv_fwd_t_slabs(op.M_in, op.K, op.Cout, op.Cin) > 1) {
-              // few slices: the product is split into offset slabs and summed by a second kernel; the BatchNorm's own
-              // small-level reduction (one launch) is cheaper than a statistics variant of that sum
-              bn_unfused[bn - ops] = 1;
-              rc = wsis_spconv_fwd_t((const float*)op.in[2], (const int32_t*)op.in[5], (const int32_t*)op.in[6],
-                                     (const float*)op.in[1], (op.flags & WSIS_OPF_FLIP) ? 1 : 0, nullptr, nullptr,
-                                     (float*)op.out[0], nullptr, op.M_out, op.M_in, op.K, op.Cout, op.Cin, rest,
-                                     rest_bytes, sync_slot(d_sync, i), stream);
-              if (rc != WSIS_OK) break;
-              goto din_done;
-            }
-            rc = wsis_spconv_fwd_t_bn((const float*)op.in[2], (const int32_t*)op.in[5], (const int32_t*)op.in[6],
-                                      (const float*)op.in[1], (op.flags & WSIS_OPF_FLIP) ? 1 : 0, (float*)op.out[0],
-                                      (float*)const_cast<void*>(bn->in[7]), (const float*)bn->in[0],
-                                      (const float*)bn->in[2], (const float*)bn->in[3], (const float*)bn->in[4],
-                                      (const float*)bn->in[5], bn->eps, (bn->flags & WSIS_OPF_RELU) ? 1 : 0, op.M_out,
-                                      op.M_in, op.K, op.Cout, op.Cin, rest, rest_bytes, sync_slot(d_sync, i), stream);
-          } else {   // the weight [K, Cin, Cout] is the B^T operand of the dIn product as it stands
-            rc = wsis_spconv_fwd_t((const float*)op.in[2], (const int32_t*)op.in[5], (const int32_t*)op.in[6],
-                                   (const float*)op.in[1], (op.flags & WSIS_OPF_FLIP) ? 1 : 0, nullptr, nullptr,
-                                   (float*)op.out[0], nullptr, op.M_out, op.M_in, op.K, op.Cout, op.Cin, rest, rest_bytes,
-                                   sync_slot(d_sync, i), stream);
-          }
-          if (rc != WSIS_OK) break;
-        }
-      din_done:
-        if (op.out[1] && !dw_forked) {
-          if (tail_main && side && dw_tail_on_main(ops, n, i)) {
-            // (never deferred: the batched slab sum runs on the side stream, these slabs are written on this one)
-            rc = issue_dw(op, ws, ws_bytes, stream, nullptr);
-          } else {
-            rc = dw_issue(op);
-          }
-        }
-        break;
-      }
-      case WSIS_OP_BN_RELU_BWD:
-        if ((op.flags & WSIS_OPF_STATS) && !bn_unfused[i]) {      // the producing dIn pass left the slice partials in in[7]
-          if (!op.in[7] || !(op.flags & WSIS_OPF_TRAINING)) {
-            rc = fail(WSIS_ERR_ARG, "op %d: BatchNorm backward from partials needs in[7] and training mode", i);
-            break;
-          }
-          rc = wsis_bn_bwd_from_partials((const float*)op.in[7], (op.M_in + 31) / 32, (const float*)op.in[0],
-                                         (const float*)op.in[1], (const float*)op.in[2], (const float*)op.in[3],
-                                         (const float*)op.in[4], (const float*)op.in[5], op.eps,
-                                         (op.flags & WSIS_OPF_RELU) ? 1 : 0, (float*)op.out[0], (float*)op.out[1],
-                                         (float*)op.out[2], (const float*)op.in[6], op.M_in, op.Cin, ws, ws_bytes,
-                                         sync_slot(d_sync, i), stream);
-          break;
-        }
-        rc = wsis_bn_bwd((const float*)op.in[0], (const float*)op.in[1], (const float*)op.in[2], (const float*)op.in[3],
-                         (const float*)op.in[4], (const float*)op.in[5], op.eps, (op.flags & WSIS_OPF_RELU) ? 1 : 0,
-                         (op.flags & WSIS_OPF_TRAINING) ? 1 : 0, (float*)op.out[0], (float*)op.out[1], (float*)op.out[2],
-                         (const float*)op.in[6], op.M_in, op.Cin, ws, ws_bytes, stream);
-        break;
-      default:
-        rc = fail(WSIS_ERR_ARG, "wsis_run_ops: unknown op kind");
-    }
-    if (bn_prof) bn_prof->stop();
-    }
-    if (rc != WSIS_OK) {
-      first_err = rc;
-      break;
-    }
-#if WSIS_EXPERIMENTAL
-  op_done:
-#endif
-    if (i == mark_op) {
-      // milestone: waiter_stream continues once everything issued so far -- on the caller's stream AND on the
-      // weight-gradient side stream -- has run (gradient exchange of the finished part of the flat buffer while the
-      // rest of the pass still executes)
-      SideStream* ms = side ? side : side_stream_for(st);
-      {
-        int wrc = dw_flush();               // the weight gradients up to here are FINAL behind their stream's event
-        if (wrc == WSIS_OK) wrc = drain_worker();     // the dW launches up to here are on the side stream before its event
-        if (wrc != WSIS_OK) {
-          first_err = wrc;
-          break;
-        }
-      }
-      hipError_t e = ms ? hipEventRecord(ms->mark_main, st) : hipErrorOutOfMemory;
-      if (e == hipSuccess) e = hipStreamWaitEvent(as_stream(waiter_stream), ms->mark_main, 0);
-      if (e == hipSuccess && forked) {
-        e = hipEventRecord(ms->mark_side, side->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(as_stream(waiter_stream), ms->mark_side, 0);
-      }
-      if (e != hipSuccess) {
-        first_err = fail(WSIS_ERR_HIP, "wsis_run_ops: milestone failed: %s", hipGetErrorString(e));
-        break;
-      }
-    }
-  }
-#undef RUN_LAUNCH_CHECK
-  {
-    int wrc = first_err == WSIS_OK ? dw_flush() : WSIS_OK;      // (every part of a pass finishes its own products)
-    if (wrc != WSIS_OK && first_err == WSIS_OK) first_err = wrc;
-    wrc = drain_worker();
-    if (wrc != WSIS_OK && first_err == WSIS_OK) first_err = wrc;
-  }
-  if (defer_join && first_err == WSIS_OK) {
-    if (forked) side->pending_join = true;
-    return WSIS_OK;
-  }
-  if (!forked && !side && dw_stream_enabled()) {      // a part without weight gradients of its own may owe an earlier part's join
-    SideStream* s2 = side_stream_for(st);
-    if (s2 && s2->pending_join) {
-      side = s2;
-      forked = true;
-    }
-  } else if (side && side->pending_join) {
-    forked = true;
-  }
-  if (forked) {   // join on EVERY exit path once forked: whatever follows on the caller's stream (optimizer, gradient
-                  // all-reduce, the caller's error handling) is ordered behind every dW launch already issued
-    side->pending_join = false;
-    const hipError_t e1 = hipEventRecord(side->join, side->stream);
-    const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(st, side->join, 0) : e1;
-    if (e2 != hipSuccess && first_err == WSIS_OK)
-      return fail(WSIS_ERR_HIP, "side-stream join failed: %s", hipGetErrorString(e2));
-  }
-  return first_err;
 }
 
 #if WSIS_EXPERIMENTAL

@@ -723,3 +723,54 @@ def test_warm_streams_is_idempotent_and_leaves_results_alone():
     wsis_parallel.warm_streams("cuda:0")
     l1, _ = harness.forward_loss(model, crit, batch, cfg)
     assert torch.equal(l0, l1)
+
+
+def test_error_exit_orders_the_callers_stream_behind_the_forked_weight_transposes(monkeypatch):
+    """A pass forks its weight transposes to the library's side stream and makes the caller's stream wait for them in
+    front of their first reader.  A pass that fails BEFORE that reader must wait all the same (PassRun::finish): the
+    caller hands the workspace back to the allocator next, and the side stream is still writing into it.  Op 0 is of an
+    unknown kind (sized as zero bytes, refused when it is issued); ops 1 and 2 are forward convolutions on the kernel
+    that reads B^T.  After the failed call only the CALLER's stream is synchronised: op 1's slot must hold W^T."""
+    import ctypes
+    import unet_native as un
+    import wsis_native as _n
+    from spconv import ops as sp_ops
+    for k in ("WSIS_WT_SIDE", "WSIS_DW_STREAM", "WSIS_FWD2"):
+        monkeypatch.delenv(k, raising=False)
+    lib = _n.hip()
+    dev = torch.device("cuda", 0)
+    K, C, M = 27, 32, 64            # 64 rows: two 32-row slices
+    rng = np.random.default_rng(5)
+    shape = (8, 8, 4)
+    occ = np.stack(np.unravel_index(np.sort(rng.permutation(int(np.prod(shape)))[:M]), shape), 1)
+    idx = torch.from_numpy(np.concatenate([np.zeros((M, 1), np.int64), occ], 1).astype(np.int32)).to(dev)
+    caller = torch.cuda.Stream(dev)
+    with torch.cuda.stream(caller):
+        rb = sp_ops.build_subm_rulebook(idx, shape, [3, 3, 3], [1, 1, 1])
+        X = torch.randn(M, C, device=dev)
+        W = [torch.randn(K, C, C, device=dev) for _ in range(2)]
+        Y = [torch.empty(M, C, device=dev) for _ in range(2)]
+        want = W[0].transpose(1, 2).contiguous()          # [K, Cout, Cin]
+        ops = np.zeros(3, dtype=un.OP_DTYPE)
+        ops["kind"][0] = 99
+        for j in (1, 2):
+            ops["kind"][j], ops["M_in"][j], ops["M_out"][j] = un.OP_CONV, M, M
+            ops["K"][j], ops["Cin"][j], ops["Cout"][j] = K, C, C
+            ops["inp"][j, :4] = [X.data_ptr(), rb.nbr_p.data_ptr(), _n.ptr(rb.order) or 0, W[j - 1].data_ptr()]
+            ops["out"][j, 0] = Y[j - 1].data_ptr()
+        layout = lib.wsis_debug_run_ops_layout
+        layout.restype = ctypes.c_int32
+        layout.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+        plan = np.zeros(11 + 2 * 3, dtype=np.int64)
+        assert layout(ops.ctypes.data, 3, plan.ctypes.data) == 0
+        total, wt_at, wt_off = int(plan[10]), int(plan[2]), plan[11 + 3:]
+        assert total == lib.wsis_run_ops_workspace_bytes(ops.ctypes.data, 3)
+        assert wt_off[0] == -1 and wt_off[1] == 0 and wt_off[2] == K * C * C * 4, "ops 1 and 2 read a transposed weight"
+        ws = torch.zeros(total, dtype=torch.uint8, device=dev)
+        sync = _n.sync_block(dev)
+        rc = lib.wsis_run_ops(ops.ctypes.data, 3, ws.data_ptr(), total, sync.data_ptr(), _n.stream_ptr())
+        assert rc == -1 and "unknown op kind" in lib.wsis_last_error().decode()        # WSIS_ERR_ARG, from host code
+        caller.synchronize()                                # the caller's stream ONLY
+        a = wt_at + int(wt_off[1])
+        got = ws[a:a + K * C * C * 4].view(torch.float32).reshape(K, C, C)
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32))
