@@ -343,29 +343,21 @@ __global__ void down_fill_kernel(const int32_t* __restrict__ indices, int64_t M_
 
 __device__ __forceinline__ uint32_t spread3(uint32_t x) {  // 8 bits -> every third bit
   x &= 0xffu;
-  x = (x | (x << 16)) & 0x0300F00Fu;
+  x = (x | (x << 16)) & 0x030000FFu;
   x = (x | (x << 8)) & 0x0300F00Fu;
   x = (x | (x << 4)) & 0x030C30C3u;
   x = (x | (x << 2)) & 0x09249249u;
   return x;
 }
 
-// sort key of a row: (batch, Morton code of its block of 2^bs voxels per side, set of active offsets).
-// Rows of one spatial block become neighbours (their gathers hit the same L1/L2 lines), and inside a block
-// rows with the same offset set are adjacent (whole 32-row MFMA slices skip inactive offsets).
-__global__ void tile_key_kernel(const int32_t* __restrict__ indices, const uint32_t* __restrict__ mask,
-                                int64_t M, int bs, uint64_t* __restrict__ keys, int32_t* __restrict__ iota) {
-  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < M;
-       r += (int64_t)gridDim.x * blockDim.x) {
-    const int4 c = reinterpret_cast<const int4*>(indices)[r];
-    const uint32_t mort = spread3((uint32_t)c.y >> bs) | (spread3((uint32_t)c.z >> bs) << 1) |
-                          (spread3((uint32_t)c.w >> bs) << 2);
-    keys[r] = ((uint64_t)((uint32_t)c.x & 0xffu) << 56) | ((uint64_t)(mort & 0xffffffu) << 32) |
-              (uint64_t)(mask ? mask[r] : 0u);
-    iota[r] = (int32_t)r;
-  }
-}
-
+// ---- tile order.  Sort key of a row: (table, batch, Morton code of its block of 2^bs voxels per side, set of active
+// offsets) = table << 60 | (batch & batch_mask) << 56 | morton24 << 32 | mask.  Rows of one spatial block become
+// neighbours (their gathers hit the same L1/L2 lines), and inside a block rows with the same offset set are adjacent
+// (whole 32-row MFMA slices skip inactive offsets).  ONE stable sort of the concatenated keys of up to 16 gather tables
+// leaves every table's order in its own contiguous segment (13 tables of the C2 pyramid: 13 x ~9 merge-sort launches of
+// a few microseconds each -> ~11).  One table: the table field is 0 and the batch index has all 8 bits above the
+// Morton code (batch_mask 0xff); several tables: it has 4 (batch_mask 0xf) and the table number sits in the top 4.
+//
 // ---- slice scheduling.  A launch lasts as long as its most loaded CU, and the dispatcher hands workgroup i of a launch
 // to CU i % n_cu while workgroups fit (measured, tools/conv2_stamps.py: exact for every workgroup that is resident from
 // the start; later ones go wherever a slot frees).  The 32-row slices of the locality order -- the work items of the
@@ -377,44 +369,6 @@ __global__ void tile_key_kernel(const int32_t* __restrict__ indices, const uint3
 // bands of a launch depend on its channel count), and every level is scheduled (levels 2-4 were not: their most
 // loaded CU carried 51 steps against a mean of 26).  WSIS_TILE_BAND = n > 0 puts the round-1 snake back into the order.
 constexpr int SCHED_TM = 32;
-
-__global__ __launch_bounds__(64) void tile_weight_kernel(const int32_t* __restrict__ order,
-                                                         const uint32_t* __restrict__ mask, int64_t n_tiles,
-                                                         uint32_t* __restrict__ keys, int32_t* __restrict__ ids) {
-  const int64_t t = blockIdx.x;
-  if (t >= n_tiles) return;
-  const int lane = threadIdx.x;
-  uint32_t m = lane < SCHED_TM ? mask[order[t * SCHED_TM + lane]] : 0u;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m |= __shfl_xor(m, off, 64);
-  if (lane == 0) {
-    keys[t] = 32u - (uint32_t)__popc(m);     // ascending key = descending weight
-    ids[t] = (int32_t)t;
-  }
-}
-
-__global__ void tile_permute_kernel(const int32_t* __restrict__ order_in, const int32_t* __restrict__ sorted_tiles,
-                                    int64_t M, int64_t n_tiles, int band, int32_t* __restrict__ order_out) {
-  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < M; p += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t slot = p / SCHED_TM;
-    if (slot >= n_tiles) {       // the partial tile at the end keeps its place
-      order_out[p] = order_in[p];
-      continue;
-    }
-    // snake: slot -> rank in the weight order
-    const int64_t b = slot / band, c = slot - b * band;
-    int64_t rank = slot;
-    if (b & 1) {
-      const int64_t width = min((int64_t)band, n_tiles - b * band);
-      rank = b * band + (width - 1 - c);
-    }
-    order_out[p] = order_in[(int64_t)sorted_tiles[rank] * SCHED_TM + (p - slot * SCHED_TM)];
-  }
-}
-
-// ---- batched form: the tile orders of ALL gather tables of a pyramid from one sort.  Each table's keys carry the
-// table number in their top 4 bits, so one stable sort of the concatenated keys leaves every table's order in its own
-// contiguous segment (13 tables of the C2 pyramid: 13 x ~9 merge-sort launches of a few microseconds each -> ~11).
 constexpr int TOB_MAX = 16;
 struct TileBatch {
   const int32_t* indices[TOB_MAX];
@@ -424,6 +378,7 @@ struct TileBatch {
   int band[TOB_MAX];
   int n;
   int bs;
+  uint32_t batch_mask;            // bits of the batch index that enter the key: 0xff for one table, 0xf for several
 };
 
 __device__ __forceinline__ int batch_table_of(const int64_t* base, int n, int64_t e) {
@@ -442,8 +397,8 @@ __global__ void tile_key_batch_kernel(TileBatch b, uint64_t* __restrict__ keys, 
     const int4 c = reinterpret_cast<const int4*>(b.indices[t])[r];
     const uint32_t mort = spread3((uint32_t)c.y >> b.bs) | (spread3((uint32_t)c.z >> b.bs) << 1) |
                           (spread3((uint32_t)c.w >> b.bs) << 2);
-    keys[e] = ((uint64_t)t << 60) | ((uint64_t)((uint32_t)c.x & 0xfu) << 56) | ((uint64_t)(mort & 0xffffffu) << 32) |
-              (uint64_t)(b.mask[t] ? b.mask[t][r] : 0u);
+    keys[e] = ((uint64_t)t << 60) | ((uint64_t)((uint32_t)c.x & b.batch_mask) << 56) |
+              ((uint64_t)(mort & 0xffffffu) << 32) | (uint64_t)(b.mask[t] ? b.mask[t][r] : 0u);
     iota[e] = (int32_t)r;
   }
 }
@@ -462,11 +417,13 @@ __global__ __launch_bounds__(64) void tile_weight_batch_kernel(TileBatch b, cons
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) m |= __shfl_xor(m, off, 64);
   if (lane == 0) {
-    keys[g] = ((uint32_t)t << 6) | (32u - (uint32_t)__popc(m));   // table-major, then descending weight
+    keys[g] = ((uint32_t)t << 6) | (32u - (uint32_t)__popc(m));   // table-major, then ascending key = descending weight
     ids[g] = (int32_t)tile;
   }
 }
 
+// writes the scheduled slices only: order_out must already hold the locality order (order_in is its copy), which is
+// what the rows of an unscheduled table and of the partial slice at the end of a table keep
 __global__ void tile_permute_batch_kernel(TileBatch b, const int32_t* __restrict__ order_in,
                                           const int32_t* __restrict__ sorted_tiles,
                                           int32_t* __restrict__ order_out) {
@@ -477,7 +434,8 @@ __global__ void tile_permute_batch_kernel(TileBatch b, const int32_t* __restrict
     const int64_t n_tiles = b.tile_base[t + 1] - b.tile_base[t];
     const int64_t p = e - b.base[t];
     const int64_t slot = p / SCHED_TM;
-    if (slot >= n_tiles) continue;      // table not scheduled / partial tile at the end: order_out already holds it
+    if (slot >= n_tiles) continue;
+    // snake: slot -> rank in the weight order
     const int band = b.band[t];
     const int64_t bb = slot / band, c = slot - bb * band;
     int64_t rank = slot;
@@ -489,6 +447,29 @@ __global__ void tile_permute_batch_kernel(TileBatch b, const int32_t* __restrict
   }
 }
 
+// nbrS[k][c] = nbr[k][order[c]]  (gather table with its columns in tile order), up to 16 tables in one launch
+constexpr int PACK_MAX = 16;
+struct PackBatch {
+  const int32_t* nbr[PACK_MAX];
+  const int32_t* order[PACK_MAX];
+  int32_t* out[PACK_MAX];
+  int64_t M[PACK_MAX];
+  int64_t base[PACK_MAX + 1];   // first element (K*M entries per table) in the concatenated index space
+  int n;
+};
+
+__global__ void rulebook_pack_batch_kernel(PackBatch b) {
+  const int64_t total = b.base[b.n];
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total;
+       e += (int64_t)gridDim.x * blockDim.x) {
+    const int t = batch_table_of(b.base, b.n, e);
+    const int64_t u = e - b.base[t], M = b.M[t];
+    const int64_t k = u / M;
+    const int64_t c = u - k * M;
+    b.out[t][u] = b.nbr[t][k * M + b.order[t][c]];
+  }
+}
+
 int sched_band() {      // snake period of the ORDER: none by default (the launches deal, see above)
   static int band = -1;
   if (band < 0) {
@@ -496,6 +477,34 @@ int sched_band() {      // snake period of the ORDER: none by default (the launc
     band = (e && atoi(e) > 0) ? atoi(e) : 0;
   }
   return band;
+}
+
+// WSIS_TILE_SCHED=0 switches the slice schedule off; tables below WSIS_TILE_SCHED_MIN full slices keep the plain
+// locality order (their offsets are split over blockIdx.z and the dispatch pattern differs)
+struct TileSched {
+  int on, min_tiles;
+};
+const TileSched& tile_sched_config() {
+  static const TileSched c = [] {
+    TileSched v{1, 4};
+    const char* e = tune_env("WSIS_TILE_SCHED");
+    if (e) v.on = atoi(e);
+    e = tune_env("WSIS_TILE_SCHED_MIN");
+    if (e) v.min_tiles = atoi(e);
+    return v;
+  }();
+  return c;
+}
+
+// Snake period of a table of M rows = distance, in tiles, between the consecutive workgroups of one CU.  One workgroup
+// per tile (tiles >= n_cu, no offset split): n_cu.  Fewer tiles than CUs: the launch splits the offsets over blockIdx.z
+// with workgroup id = tile + n_tiles * z, so CU c holds tiles c, c + n_cu mod n_tiles, ... of successive slices.
+int tile_band(int64_t M) {
+  const int n_cu = sched_band();
+  const int64_t grid_tiles = (M + SCHED_TM - 1) / SCHED_TM;
+  int band = n_cu <= 0 ? 0x7fffffff : grid_tiles >= n_cu ? n_cu : (grid_tiles > 0 ? (int)(n_cu % grid_tiles) : 1);
+  if (band == 0) band = (int)grid_tiles;
+  return band > 0 ? band : 1;
 }
 
 __global__ void iota_kernel(int32_t* __restrict__ p, int64_t n) {
@@ -557,6 +566,162 @@ int run_fills(const FillBatch& b, hipStream_t st) {
   for (int i = 0; i < b.n; ++i) mx = b.words[i] > mx ? b.words[i] : mx;
   hipLaunchKernelGGL(multi_fill_kernel, dim3(grid_for((int64_t)((mx + 3) / 4), 256), b.n), dim3(256), 0, st, b);
   WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+// sorted unique output keys of a strided convolution: candidate keys + radix sort + unique
+int down_keys_sorted(const int32_t* d_indices_in, int64_t M_in, const int32_t* h_in_shape3,
+                     const int32_t* h_out_shape3, const int32_t* h_ksize3,
+                     const int32_t* h_stride3, const int32_t* h_pad3, int64_t* d_cand,
+                     int64_t* d_out_keys, int32_t* d_count, void* d_ws, int64_t ws_bytes,
+                     void* stream, int32_t batch_limit) {
+  WSIS_REQUIRE(M_in >= 0 && h_in_shape3 && h_out_shape3 && h_ksize3 && h_stride3 && h_pad3 && d_count,
+               "bad args");
+  hipStream_t st = as_stream(stream);
+  WSIS_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(int32_t), st));
+  if (M_in == 0) return WSIS_OK;
+  WSIS_REQUIRE(d_indices_in && d_cand && d_out_keys && d_ws, "null pointer");
+  Geo g;
+  WSIS_REQUIRE(fill_geo(g, h_in_shape3, h_out_shape3, h_ksize3, h_stride3, h_pad3) == 0, "bad geometry");
+  const int64_t n_cand = wsis_rulebook_down_ncand(M_in, h_ksize3, h_stride3, h_pad3);
+  bool fast_b = true;
+  for (int j = 0; j < 3; ++j) fast_b = fast_b && h_ksize3[j] == h_stride3[j] && h_pad3[j] == 0;
+  const int fast = fast_b ? 1 : 0;
+  // invalid candidates carry the largest int64 so they sort behind every real linear index
+  const int64_t invalid = INT64_MAX;
+  hipLaunchKernelGGL(down_cand_kernel, dim3(grid_for(M_in, 256)), dim3(256), 0, st, d_indices_in, M_in, g,
+                     fast, invalid, d_cand, batch_limit);
+  WSIS_LAUNCH_CHECK();
+  char* ws = static_cast<char*>(d_ws);
+  int64_t* d_sorted = reinterpret_cast<int64_t*>(ws);
+  size_t off = align256((size_t)n_cand * 8);
+  WSIS_REQUIRE((int64_t)off < ws_bytes, "workspace too small");
+  void* d_temp = ws + off;
+  size_t temp_bytes = (size_t)ws_bytes - off;
+  size_t need = 0;
+  WSIS_HIP_CHECK(rocprim::radix_sort_keys(nullptr, need, d_cand, d_sorted, (size_t)n_cand, 0, 64, st));
+  WSIS_REQUIRE(need <= temp_bytes, "workspace too small for sort");
+  const int end_bit = 64;
+  WSIS_HIP_CHECK(rocprim::radix_sort_keys(d_temp, temp_bytes, d_cand, d_sorted, (size_t)n_cand, 0,
+                                          end_bit, st));
+  need = 0;
+  WSIS_HIP_CHECK(rocprim::unique(nullptr, need, d_sorted, d_out_keys, d_count, (size_t)n_cand,
+                                 rocprim::equal_to<int64_t>(), st));
+  WSIS_REQUIRE(need <= temp_bytes, "workspace too small for unique");
+  WSIS_HIP_CHECK(rocprim::unique(d_temp, temp_bytes, d_sorted, d_out_keys, d_count, (size_t)n_cand,
+                                 rocprim::equal_to<int64_t>(), st));
+  hipLaunchKernelGGL(down_fix_count_kernel, dim3(1), dim3(64), 0, st, d_out_keys, invalid, d_count);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+// bitmap form of wsis_rulebook_down_keys (see down_mark_kernel); false: does not apply, nothing was issued
+bool down_keys_bitmap(const int32_t* d_indices_in, int64_t M_in, const int32_t* h_in_shape3, const int32_t* h_out_shape3,
+                      const int32_t* k, const int32_t* s3, const int32_t* p, int32_t batch_size, int64_t* d_out_keys,
+                      int32_t* d_count, void* d_ws, int64_t ws_bytes, hipStream_t st, int* rc_out) {
+  *rc_out = WSIS_OK;
+  for (int j = 0; j < 3; ++j)
+    if (k[j] != s3[j] || p[j] != 0) return false;
+  if (batch_size < 1 || M_in < 1 || !d_ws) return false;
+  const int64_t n_cells = (int64_t)batch_size * h_out_shape3[0] * h_out_shape3[1] * h_out_shape3[2];
+  if (n_cells < 1 || n_cells > ((int64_t)1 << 31)) return false;
+  const int64_t n_words = (n_cells + 31) >> 5;
+  const int64_t n_chunks = (n_words + BM_WORDS_PER_WG - 1) / BM_WORDS_PER_WG;
+  const int64_t need = (int64_t)align256((size_t)n_words * 4) + (int64_t)align256((size_t)n_chunks * 4);
+  if (need > ws_bytes || n_chunks > (1 << 22)) return false;
+  Geo g;
+  if (fill_geo(g, h_in_shape3, h_out_shape3, k, s3, p) != 0) return false;
+  uint32_t* bitmap = static_cast<uint32_t*>(d_ws);
+  int32_t* chunk = reinterpret_cast<int32_t*>(static_cast<char*>(d_ws) + align256((size_t)n_words * 4));
+  auto fail_hip = [&](hipError_t e) {
+    *rc_out = fail(WSIS_ERR_HIP, "down_keys_bitmap: %s", hipGetErrorString(e));
+    return true;
+  };
+  hipError_t e = hipMemsetAsync(bitmap, 0, (size_t)n_words * 4, st);
+  if (e != hipSuccess) return fail_hip(e);
+  hipLaunchKernelGGL(down_mark_kernel, dim3(grid_for(M_in, 256)), dim3(256), 0, st, d_indices_in, M_in, g, n_cells, bitmap);
+  hipLaunchKernelGGL(bitmap_count_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, bitmap, n_words, chunk);
+  hipLaunchKernelGGL(bitmap_scan_kernel, dim3(1), dim3(256), 0, st, chunk, (int)n_chunks, d_count);
+  hipLaunchKernelGGL(bitmap_emit_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, bitmap, n_words, chunk, d_out_keys);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e);
+  return true;
+}
+
+// layout: [keys N*8][keys_out N*8][iota N*4][temp]; the slice schedule reuses keys / keys_out after the sort
+int64_t tile_order_workspace_bytes(int64_t N) {
+  if (N < 0) return -1;
+  if (N == 0) return 256;
+  size_t sort_bytes = 0;
+  uint64_t* kp = nullptr;
+  int32_t* vp = nullptr;
+  if (rocprim::radix_sort_pairs(nullptr, sort_bytes, kp, kp, vp, vp, (size_t)N, 0, 64, (hipStream_t)0) !=
+      hipSuccess)
+    return -1;
+  return (int64_t)(2 * align256((size_t)N * 8) + align256((size_t)N * 4) + align256(sort_bytes) + 256);
+}
+
+// the tile orders of n >= 1 gather tables, concatenated in d_order_all (see TileBatch for the key)
+int tile_order_tables(int n, const void* const* h_indices, const void* const* h_mask, const int64_t* h_M,
+                      int block_shift, uint32_t batch_mask, int32_t* d_order_all, void* d_ws, int64_t ws_bytes,
+                      void* stream) {
+  const TileSched& sched = tile_sched_config();
+  TileBatch b;
+  b.n = n;
+  b.bs = block_shift;
+  b.batch_mask = batch_mask;
+  b.base[0] = b.tile_base[0] = 0;
+  for (int t = 0; t < n; ++t) {
+    WSIS_REQUIRE(h_M[t] >= 0 && (h_M[t] == 0 || h_indices[t]), "bad table");
+    b.indices[t] = static_cast<const int32_t*>(h_indices[t]);
+    b.mask[t] = static_cast<const uint32_t*>(h_mask[t]);
+    b.base[t + 1] = b.base[t] + h_M[t];
+    const int64_t n_tiles = h_M[t] / SCHED_TM;
+    const bool on = sched.on && b.mask[t] && n_tiles >= sched.min_tiles;
+    b.tile_base[t + 1] = b.tile_base[t] + (on ? n_tiles : 0);
+    b.band[t] = tile_band(h_M[t]);
+  }
+  const int64_t N = b.base[n];
+  if (N == 0) return WSIS_OK;
+  WSIS_REQUIRE(d_order_all && d_ws, "null pointer");
+  hipStream_t st = as_stream(stream);
+  char* ws = static_cast<char*>(d_ws);
+  const size_t a8 = align256((size_t)N * 8), a4 = align256((size_t)N * 4);
+  WSIS_REQUIRE((int64_t)(2 * a8 + a4) < ws_bytes, "workspace too small");
+  uint64_t* keys = reinterpret_cast<uint64_t*>(ws);
+  uint64_t* keys_out = reinterpret_cast<uint64_t*>(ws + a8);
+  int32_t* iota = reinterpret_cast<int32_t*>(ws + 2 * a8);
+  void* temp = ws + 2 * a8 + a4;
+  size_t temp_bytes = (size_t)ws_bytes - (2 * a8 + a4);
+  hipLaunchKernelGGL(tile_key_batch_kernel, dim3(grid_for(N, 256)), dim3(256), 0, st, b, keys, iota);
+  WSIS_LAUNCH_CHECK();
+  size_t need = 0;
+  WSIS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need, keys, keys_out, iota, d_order_all, (size_t)N, 0, 64, st));
+  WSIS_REQUIRE(need <= temp_bytes, "workspace too small for sort");
+  WSIS_HIP_CHECK(rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_out, iota, d_order_all, (size_t)N, 0, 64, st));
+  const int64_t T = b.tile_base[n];
+  if (T > 0) {
+    // the sort is done: keys (N*8 bytes) takes the copy of the locality order, keys_out the four arrays of the tile sort
+    int32_t* ord0 = reinterpret_cast<int32_t*>(keys);                       // N ints
+    uint32_t* tkeys = reinterpret_cast<uint32_t*>(keys_out);                // T each, 4 arrays
+    uint32_t* tkeys_out = tkeys + T;
+    int32_t* tids = reinterpret_cast<int32_t*>(tkeys_out + T);
+    int32_t* tsorted = tids + T;
+    WSIS_REQUIRE((size_t)T * 16 <= a8, "workspace too small for the tile schedule");
+    // d_order_all keeps the locality order: the permute kernel overwrites the scheduled slices only, so unscheduled
+    // tables and the partial slice at the end of a table are final already
+    WSIS_HIP_CHECK(hipMemcpyAsync(ord0, d_order_all, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(tile_weight_batch_kernel, dim3((unsigned)T), dim3(64), 0, st, b, ord0, tkeys, tids);
+    WSIS_LAUNCH_CHECK();
+    const int end_bit = 6 + (n > 1 ? bits_for(n - 1) : 0);      // weight key: table << 6 | 32 - weight
+    size_t need2 = 0;
+    WSIS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need2, tkeys, tkeys_out, tids, tsorted, (size_t)T, 0, end_bit, st));
+    WSIS_REQUIRE(need2 <= temp_bytes, "workspace too small for the tile sort");
+    WSIS_HIP_CHECK(rocprim::radix_sort_pairs(temp, temp_bytes, tkeys, tkeys_out, tids, tsorted, (size_t)T, 0, end_bit, st));
+    hipLaunchKernelGGL(tile_permute_batch_kernel, dim3(grid_for(N, 256)), dim3(256), 0, st, b, ord0, tsorted,
+                       d_order_all);
+    WSIS_LAUNCH_CHECK();
+  }
   return WSIS_OK;
 }
 
@@ -631,13 +796,6 @@ int64_t wsis_rulebook_down_workspace_bytes(int64_t n_cand) {
                    256);
 }
 
-namespace {
-int down_keys_sorted(const int32_t* d_indices_in, int64_t M_in, const int32_t* h_in_shape3,
-                     const int32_t* h_out_shape3, const int32_t* h_ksize3,
-                     const int32_t* h_stride3, const int32_t* h_pad3, int64_t* d_cand,
-                     int64_t* d_out_keys, int32_t* d_count, void* d_ws, int64_t ws_bytes,
-                     void* stream, int32_t batch_limit);
-}
 int wsis_rulebook_down_keys(const int32_t* d_indices_in, int64_t M_in, const int32_t* h_in_shape3,
                             const int32_t* h_out_shape3, const int32_t* h_ksize3,
                             const int32_t* h_stride3, const int32_t* h_pad3, int64_t* d_cand,
@@ -647,88 +805,6 @@ int wsis_rulebook_down_keys(const int32_t* d_indices_in, int64_t M_in, const int
   return down_keys_sorted(d_indices_in, M_in, h_in_shape3, h_out_shape3, h_ksize3, h_stride3, h_pad3, d_cand, d_out_keys,
                           d_count, d_ws, ws_bytes, stream, 0);
 }
-namespace {
-int down_keys_sorted(const int32_t* d_indices_in, int64_t M_in, const int32_t* h_in_shape3,
-                     const int32_t* h_out_shape3, const int32_t* h_ksize3,
-                     const int32_t* h_stride3, const int32_t* h_pad3, int64_t* d_cand,
-                     int64_t* d_out_keys, int32_t* d_count, void* d_ws, int64_t ws_bytes,
-                     void* stream, int32_t batch_limit) {
-  WSIS_REQUIRE(M_in >= 0 && h_in_shape3 && h_out_shape3 && h_ksize3 && h_stride3 && h_pad3 && d_count,
-               "bad args");
-  hipStream_t st = as_stream(stream);
-  WSIS_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(int32_t), st));
-  if (M_in == 0) return WSIS_OK;
-  WSIS_REQUIRE(d_indices_in && d_cand && d_out_keys && d_ws, "null pointer");
-  Geo g;
-  WSIS_REQUIRE(fill_geo(g, h_in_shape3, h_out_shape3, h_ksize3, h_stride3, h_pad3) == 0, "bad geometry");
-  const int64_t n_cand = wsis_rulebook_down_ncand(M_in, h_ksize3, h_stride3, h_pad3);
-  bool fast_b = true;
-  for (int j = 0; j < 3; ++j) fast_b = fast_b && h_ksize3[j] == h_stride3[j] && h_pad3[j] == 0;
-  const int fast = fast_b ? 1 : 0;
-  // invalid candidates carry the largest int64 so they sort behind every real linear index
-  const int64_t invalid = INT64_MAX;
-  hipLaunchKernelGGL(down_cand_kernel, dim3(grid_for(M_in, 256)), dim3(256), 0, st, d_indices_in, M_in, g,
-                     fast, invalid, d_cand, batch_limit);
-  WSIS_LAUNCH_CHECK();
-  char* ws = static_cast<char*>(d_ws);
-  int64_t* d_sorted = reinterpret_cast<int64_t*>(ws);
-  size_t off = align256((size_t)n_cand * 8);
-  WSIS_REQUIRE((int64_t)off < ws_bytes, "workspace too small");
-  void* d_temp = ws + off;
-  size_t temp_bytes = (size_t)ws_bytes - off;
-  size_t need = 0;
-  WSIS_HIP_CHECK(rocprim::radix_sort_keys(nullptr, need, d_cand, d_sorted, (size_t)n_cand, 0, 64, st));
-  WSIS_REQUIRE(need <= temp_bytes, "workspace too small for sort");
-  const int end_bit = 64;
-  WSIS_HIP_CHECK(rocprim::radix_sort_keys(d_temp, temp_bytes, d_cand, d_sorted, (size_t)n_cand, 0,
-                                          end_bit, st));
-  need = 0;
-  WSIS_HIP_CHECK(rocprim::unique(nullptr, need, d_sorted, d_out_keys, d_count, (size_t)n_cand,
-                                 rocprim::equal_to<int64_t>(), st));
-  WSIS_REQUIRE(need <= temp_bytes, "workspace too small for unique");
-  WSIS_HIP_CHECK(rocprim::unique(d_temp, temp_bytes, d_sorted, d_out_keys, d_count, (size_t)n_cand,
-                                 rocprim::equal_to<int64_t>(), st));
-  hipLaunchKernelGGL(down_fix_count_kernel, dim3(1), dim3(64), 0, st, d_out_keys, invalid, d_count);
-  WSIS_LAUNCH_CHECK();
-  return WSIS_OK;
-}
-}  // namespace
-
-namespace {
-// bitmap form of wsis_rulebook_down_keys (see down_mark_kernel); false: does not apply, nothing was issued
-bool down_keys_bitmap(const int32_t* d_indices_in, int64_t M_in, const int32_t* h_in_shape3, const int32_t* h_out_shape3,
-                      const int32_t* k, const int32_t* s3, const int32_t* p, int32_t batch_size, int64_t* d_out_keys,
-                      int32_t* d_count, void* d_ws, int64_t ws_bytes, hipStream_t st, int* rc_out) {
-  *rc_out = WSIS_OK;
-  for (int j = 0; j < 3; ++j)
-    if (k[j] != s3[j] || p[j] != 0) return false;
-  if (batch_size < 1 || M_in < 1 || !d_ws) return false;
-  const int64_t n_cells = (int64_t)batch_size * h_out_shape3[0] * h_out_shape3[1] * h_out_shape3[2];
-  if (n_cells < 1 || n_cells > ((int64_t)1 << 31)) return false;
-  const int64_t n_words = (n_cells + 31) >> 5;
-  const int64_t n_chunks = (n_words + BM_WORDS_PER_WG - 1) / BM_WORDS_PER_WG;
-  const int64_t need = (int64_t)align256((size_t)n_words * 4) + (int64_t)align256((size_t)n_chunks * 4);
-  if (need > ws_bytes || n_chunks > (1 << 22)) return false;
-  Geo g;
-  if (fill_geo(g, h_in_shape3, h_out_shape3, k, s3, p) != 0) return false;
-  uint32_t* bitmap = static_cast<uint32_t*>(d_ws);
-  int32_t* chunk = reinterpret_cast<int32_t*>(static_cast<char*>(d_ws) + align256((size_t)n_words * 4));
-  auto fail_hip = [&](hipError_t e) {
-    *rc_out = fail(WSIS_ERR_HIP, "down_keys_bitmap: %s", hipGetErrorString(e));
-    return true;
-  };
-  hipError_t e = hipMemsetAsync(bitmap, 0, (size_t)n_words * 4, st);
-  if (e != hipSuccess) return fail_hip(e);
-  hipLaunchKernelGGL(down_mark_kernel, dim3(grid_for(M_in, 256)), dim3(256), 0, st, d_indices_in, M_in, g, n_cells, bitmap);
-  hipLaunchKernelGGL(bitmap_count_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, bitmap, n_words, chunk);
-  hipLaunchKernelGGL(bitmap_scan_kernel, dim3(1), dim3(256), 0, st, chunk, (int)n_chunks, d_count);
-  hipLaunchKernelGGL(bitmap_emit_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, bitmap, n_words, chunk, d_out_keys);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e);
-  return true;
-}
-}  // namespace
-
 int wsis_rulebook_down_fill(const int32_t* d_indices_in, int64_t M_in, const int32_t* h_in_shape3,
                             const int32_t* h_out_shape3, const int32_t* h_ksize3,
                             const int32_t* h_stride3, const int32_t* h_pad3,
@@ -775,92 +851,18 @@ int wsis_rulebook_down_fill(const int32_t* d_indices_in, int64_t M_in, const int
   return WSIS_OK;
 }
 
-int64_t wsis_tile_order_workspace_bytes(int64_t M) {
-  if (M < 0) return -1;
-  if (M == 0) return 256;
-  size_t sort_bytes = 0;
-  uint64_t* kp = nullptr;
-  int32_t* vp = nullptr;
-  if (rocprim::radix_sort_pairs(nullptr, sort_bytes, kp, kp, vp, vp, (size_t)M, 0, 64, (hipStream_t)0) !=
-      hipSuccess)
-    return -1;
-  // layout: [keys M*8][keys_out M*8][iota M*4][temp]; the tile scheduling reuses the two key arrays afterwards
-  return (int64_t)(2 * align256((size_t)M * 8) + align256((size_t)M * 4) + align256(sort_bytes) + 256);
-}
+int64_t wsis_tile_order_workspace_bytes(int64_t M) { return tile_order_workspace_bytes(M); }
+int64_t wsis_tile_order_batch_workspace_bytes(int64_t N) { return tile_order_workspace_bytes(N); }
 
 int wsis_tile_order(const int32_t* d_indices, const uint32_t* d_mask, int64_t M, int32_t block_shift,
                     int32_t* d_order, void* d_ws, int64_t ws_bytes, void* stream) {
   WSIS_REQUIRE(M >= 0 && block_shift >= 0 && block_shift < 16, "bad args");
   if (M == 0) return WSIS_OK;
   WSIS_REQUIRE(d_indices && d_order && d_ws, "null pointer");
-  hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(d_ws);
-  const size_t a8 = align256((size_t)M * 8), a4 = align256((size_t)M * 4);
-  WSIS_REQUIRE((int64_t)(2 * a8 + a4) < ws_bytes, "workspace too small");
-  uint64_t* keys = reinterpret_cast<uint64_t*>(ws);
-  uint64_t* keys_out = reinterpret_cast<uint64_t*>(ws + a8);
-  int32_t* iota = reinterpret_cast<int32_t*>(ws + 2 * a8);
-  void* temp = ws + 2 * a8 + a4;
-  size_t temp_bytes = (size_t)ws_bytes - (2 * a8 + a4);
-  hipLaunchKernelGGL(tile_key_kernel, dim3(grid_for(M, 256)), dim3(256), 0, st, d_indices, d_mask, M,
-                     (int)block_shift, keys, iota);
-  WSIS_LAUNCH_CHECK();
-  size_t need = 0;
-  WSIS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need, keys, keys_out, iota, d_order, (size_t)M, 0, 64, st));
-  WSIS_REQUIRE(need <= temp_bytes, "workspace too small for sort");
-  WSIS_HIP_CHECK(rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_out, iota, d_order, (size_t)M, 0, 64, st));
-
-  // ---- tile scheduling (WSIS_TILE_SCHED=0 switches it off; levels below WSIS_TILE_SCHED_MIN full tiles keep the
-  //      plain locality order: their offsets are split over blockIdx.z and the dispatch pattern differs)
-  static int sched = -1, sched_min = 4;
-  if (sched < 0) {
-    const char* e = tune_env("WSIS_TILE_SCHED");
-    sched = e ? atoi(e) : 1;
-    e = tune_env("WSIS_TILE_SCHED_MIN");
-    if (e) sched_min = atoi(e);
-  }
-  const int64_t n_tiles = M / SCHED_TM;
-  if (sched && d_mask && n_tiles >= sched_min) {
-    // the sort is done: keys (M*8 bytes) holds the old order copy + tile arrays, keys_out the tile sort scratch
-    int32_t* ord0 = reinterpret_cast<int32_t*>(keys);                       // M ints (<= half of the region)
-    uint32_t* tkeys = reinterpret_cast<uint32_t*>(keys_out);                // n_tiles each, 4 arrays
-    uint32_t* tkeys_out = tkeys + n_tiles;
-    int32_t* tids = reinterpret_cast<int32_t*>(tkeys_out + n_tiles);
-    int32_t* tsorted = tids + n_tiles;
-    WSIS_REQUIRE((size_t)n_tiles * 16 <= a8, "workspace too small for the tile schedule");
-    WSIS_HIP_CHECK(hipMemcpyAsync(ord0, d_order, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(tile_weight_kernel, dim3((unsigned)n_tiles), dim3(64), 0, st, ord0, d_mask, n_tiles, tkeys,
-                       tids);
-    WSIS_LAUNCH_CHECK();
-    size_t need2 = 0;
-    WSIS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need2, tkeys, tkeys_out, tids, tsorted, (size_t)n_tiles, 0, 6, st));
-    WSIS_REQUIRE(need2 <= temp_bytes, "workspace too small for the tile sort");
-    WSIS_HIP_CHECK(rocprim::radix_sort_pairs(temp, temp_bytes, tkeys, tkeys_out, tids, tsorted, (size_t)n_tiles, 0, 6, st));
-    // Snake period = distance, in tiles, between the consecutive workgroups of one CU.  One workgroup per tile
-    // (n_tiles >= n_cu, no offset split): n_cu.  Fewer tiles than CUs: the launch splits the offsets over blockIdx.z
-    // with workgroup id = tile + n_tiles * z, so CU c holds tiles c, c + n_cu mod n_tiles, ... of successive slices.
-    const int n_cu = sched_band();
-    const int64_t grid_tiles = (M + SCHED_TM - 1) / SCHED_TM;
-    int band = n_cu <= 0 ? 0x7fffffff : grid_tiles >= n_cu ? n_cu : (int)(n_cu % grid_tiles);
-    if (band == 0) band = (int)grid_tiles;
-    hipLaunchKernelGGL(tile_permute_kernel, dim3(grid_for(M, 256)), dim3(256), 0, st, ord0, tsorted, M, n_tiles,
-                       band, d_order);
-    WSIS_LAUNCH_CHECK();
-  }
-  return WSIS_OK;
-}
-
-int64_t wsis_tile_order_batch_workspace_bytes(int64_t N) {
-  if (N < 0) return -1;
-  if (N == 0) return 256;
-  size_t sort_bytes = 0;
-  uint64_t* kp = nullptr;
-  int32_t* vp = nullptr;
-  if (rocprim::radix_sort_pairs(nullptr, sort_bytes, kp, kp, vp, vp, (size_t)N, 0, 64, (hipStream_t)0) !=
-      hipSuccess)
-    return -1;
-  // layout: [keys N*8][keys_out N*8][iota N*4][temp]; the tile schedule reuses keys / keys_out after the sort
-  return (int64_t)(2 * align256((size_t)N * 8) + align256((size_t)N * 4) + align256(sort_bytes) + 256);
+  const void* indices = d_indices;
+  const void* mask = d_mask;
+  // one table: its field of the key is 0 and the batch index keeps 8 bits (batches of more than 16 scenes)
+  return tile_order_tables(1, &indices, &mask, &M, block_shift, 0xffu, d_order, d_ws, ws_bytes, stream);
 }
 
 int wsis_tile_order_batch(int32_t n, const void* const* h_indices, const void* const* h_mask, const int64_t* h_M,
@@ -870,72 +872,7 @@ int wsis_tile_order_batch(int32_t n, const void* const* h_indices, const void* c
   WSIS_REQUIRE(batch_size >= 1 && batch_size <= 16, "the batched tile order packs the batch index into 4 bits");
   if (n == 0) return WSIS_OK;
   WSIS_REQUIRE(h_indices && h_mask && h_M, "null pointer");
-  TileBatch b;
-  b.n = n;
-  b.bs = block_shift;
-  b.base[0] = 0;
-  for (int t = 0; t < n; ++t) {
-    WSIS_REQUIRE(h_M[t] >= 0 && (h_M[t] == 0 || h_indices[t]), "bad table");
-    b.indices[t] = static_cast<const int32_t*>(h_indices[t]);
-    b.mask[t] = static_cast<const uint32_t*>(h_mask[t]);
-    b.base[t + 1] = b.base[t] + h_M[t];
-  }
-  const int64_t N = b.base[n];
-  if (N == 0) return WSIS_OK;
-  WSIS_REQUIRE(d_order_all && d_ws, "null pointer");
-  hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(d_ws);
-  const size_t a8 = align256((size_t)N * 8), a4 = align256((size_t)N * 4);
-  WSIS_REQUIRE((int64_t)(2 * a8 + a4) < ws_bytes, "workspace too small");
-  uint64_t* keys = reinterpret_cast<uint64_t*>(ws);
-  uint64_t* keys_out = reinterpret_cast<uint64_t*>(ws + a8);
-  int32_t* iota = reinterpret_cast<int32_t*>(ws + 2 * a8);
-  void* temp = ws + 2 * a8 + a4;
-  size_t temp_bytes = (size_t)ws_bytes - (2 * a8 + a4);
-  static int sched = -1, sched_min = 4;
-  if (sched < 0) {
-    const char* e = tune_env("WSIS_TILE_SCHED");
-    sched = e ? atoi(e) : 1;
-    e = tune_env("WSIS_TILE_SCHED_MIN");
-    if (e) sched_min = atoi(e);
-  }
-  const int n_cu = sched_band();
-  b.tile_base[0] = 0;
-  for (int t = 0; t < n; ++t) {
-    const int64_t n_tiles = h_M[t] / SCHED_TM;
-    const bool on = sched && b.mask[t] && n_tiles >= sched_min;
-    b.tile_base[t + 1] = b.tile_base[t] + (on ? n_tiles : 0);
-    const int64_t grid_tiles = (h_M[t] + SCHED_TM - 1) / SCHED_TM;
-    int band = n_cu <= 0 ? 0x7fffffff : grid_tiles >= n_cu ? n_cu : (grid_tiles > 0 ? (int)(n_cu % grid_tiles) : 1);
-    if (band == 0) band = (int)grid_tiles;
-    b.band[t] = band > 0 ? band : 1;
-  }
-  hipLaunchKernelGGL(tile_key_batch_kernel, dim3(grid_for(N, 256)), dim3(256), 0, st, b, keys, iota);
-  WSIS_LAUNCH_CHECK();
-  size_t need = 0;
-  WSIS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need, keys, keys_out, iota, d_order_all, (size_t)N, 0, 64, st));
-  WSIS_REQUIRE(need <= temp_bytes, "workspace too small for sort");
-  WSIS_HIP_CHECK(rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_out, iota, d_order_all, (size_t)N, 0, 64, st));
-  const int64_t T = b.tile_base[n];
-  if (T > 0) {
-    int32_t* ord0 = reinterpret_cast<int32_t*>(keys);                       // N ints
-    uint32_t* tkeys = reinterpret_cast<uint32_t*>(keys_out);                // T each, 4 arrays
-    uint32_t* tkeys_out = tkeys + T;
-    int32_t* tids = reinterpret_cast<int32_t*>(tkeys_out + T);
-    int32_t* tsorted = tids + T;
-    WSIS_REQUIRE((size_t)T * 16 <= a8, "workspace too small for the tile schedule");
-    WSIS_HIP_CHECK(hipMemcpyAsync(ord0, d_order_all, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(tile_weight_batch_kernel, dim3((unsigned)T), dim3(64), 0, st, b, ord0, tkeys, tids);
-    WSIS_LAUNCH_CHECK();
-    size_t need2 = 0;
-    WSIS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need2, tkeys, tkeys_out, tids, tsorted, (size_t)T, 0, 10, st));
-    WSIS_REQUIRE(need2 <= temp_bytes, "workspace too small for the tile sort");
-    WSIS_HIP_CHECK(rocprim::radix_sort_pairs(temp, temp_bytes, tkeys, tkeys_out, tids, tsorted, (size_t)T, 0, 10, st));
-    hipLaunchKernelGGL(tile_permute_batch_kernel, dim3(grid_for(N, 256)), dim3(256), 0, st, b, ord0, tsorted,
-                       d_order_all);
-    WSIS_LAUNCH_CHECK();
-  }
-  return WSIS_OK;
+  return tile_order_tables(n, h_indices, h_mask, h_M, block_shift, 0xfu, d_order_all, d_ws, ws_bytes, stream);
 }
 
 int64_t wsis_mask_order_workspace_bytes(int64_t M) {
@@ -974,6 +911,42 @@ int wsis_mask_order(const uint32_t* d_mask, int64_t M, int32_t* d_order, void* d
   return WSIS_OK;
 }
 
+int wsis_rulebook_pack_batch(int32_t n, const void* const* h_nbr, const void* const* h_order,
+                             void* const* h_nbr_packed, const int64_t* h_M, const int32_t* h_K, void* stream) {
+  WSIS_REQUIRE(n >= 0 && n <= PACK_MAX, "at most 16 tables per call");
+  if (n == 0) return WSIS_OK;
+  WSIS_REQUIRE(h_nbr && h_order && h_nbr_packed && h_M && h_K, "null pointer");
+  PackBatch b;
+  b.n = 0;
+  b.base[0] = 0;
+  for (int t = 0; t < n; ++t) {
+    WSIS_REQUIRE(h_M[t] >= 0 && h_K[t] >= 1, "bad sizes");
+    if (h_M[t] == 0) continue;
+    WSIS_REQUIRE(h_nbr[t] && h_order[t] && h_nbr_packed[t], "null table pointer");
+    b.nbr[b.n] = static_cast<const int32_t*>(h_nbr[t]);
+    b.order[b.n] = static_cast<const int32_t*>(h_order[t]);
+    b.out[b.n] = static_cast<int32_t*>(h_nbr_packed[t]);
+    b.M[b.n] = h_M[t];
+    b.base[b.n + 1] = b.base[b.n] + h_M[t] * h_K[t];
+    ++b.n;
+  }
+  if (b.n == 0) return WSIS_OK;
+  hipLaunchKernelGGL(rulebook_pack_batch_kernel, dim3(grid_for(b.base[b.n], 256)), dim3(256), 0, as_stream(stream), b);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+int wsis_rulebook_pack(const int32_t* d_nbr, const int32_t* d_order, int32_t* d_nbr_packed, int64_t M,
+                       int32_t K, void* stream) {
+  WSIS_REQUIRE(M >= 0 && K >= 1, "bad sizes");
+  if (M == 0) return WSIS_OK;
+  WSIS_REQUIRE(d_nbr && d_order && d_nbr_packed, "null pointer");
+  const void* nbr = d_nbr;
+  const void* order = d_order;
+  void* out = d_nbr_packed;
+  return wsis_rulebook_pack_batch(1, &nbr, &order, &out, &M, &K, stream);
+}
+
 
 // ---- the whole rulebook pyramid of a UBlock from ONE call -------------------------------------------------------
 // SubM k3 p1 table per level + SparseConv3d k2 s2 tables between levels (sparse_unet3d.py:130,261,292; [UPSTREAM
@@ -994,6 +967,24 @@ inline int64_t pow2_cap(int64_t m) {
 struct PyrLayout {
   int64_t off[8][WSIS_PYR_FIELDS];
   int64_t tile_ws, tile_ws_bytes, order_all, total;
+};
+// the gather tables of a pyramid in the argument form of wsis_tile_order_batch / wsis_rulebook_pack_batch
+struct PyrTables {
+  const void* idx[TOB_MAX];
+  const void* mask[TOB_MAX];
+  const void* nbr[TOB_MAX];
+  const void* order[TOB_MAX];
+  void* out[TOB_MAX];
+  int64_t M[TOB_MAX];
+  int32_t K[TOB_MAX];
+  int n = 0, n_rows = 0;      // tables, tables with rows
+  // (3 * n_levels - 2 calls per pyramid: wsis_rulebook_pyramid requires that to be <= TOB_MAX before the first one)
+  void add(const void* indices, int64_t rows, int32_t k, const void* mask_, const void* nbr_, const void* order_,
+           void* out_) {
+    idx[n] = indices, mask[n] = mask_, nbr[n] = nbr_, order[n] = order_, out[n] = out_, M[n] = rows, K[n] = k;
+    n_rows += rows > 0;
+    ++n;
+  }
 };
 int pyr_layout(int64_t M0, const int64_t* counts, int n_levels, PyrLayout& L) {
   if (n_levels < 1 || n_levels > 8 || M0 < 0) return -1;
@@ -1070,7 +1061,7 @@ int wsis_rulebook_pyramid(const int32_t* d_indices0, int64_t M0, const int32_t* 
                           int32_t n_levels, int32_t batch_size, int32_t block_shift, void* d_arena, int64_t arena_bytes,
                           void* stream) {
   WSIS_REQUIRE(h_shape3 && d_arena && (M0 == 0 || d_indices0), "null pointer");
-  WSIS_REQUIRE(n_levels <= 5 || n_levels * 3 - 2 <= 16, "at most 16 gather tables per batched tile order");
+  WSIS_REQUIRE(n_levels * 3 - 2 <= TOB_MAX, "at most 16 gather tables per batched tile order");      // bounds PyrTables
   PyrLayout L;
   WSIS_REQUIRE((n_levels <= 1 || h_counts) && pyr_layout(M0, h_counts, n_levels, L) == 0, "bad level counts");
   WSIS_REQUIRE(arena_bytes >= L.total && (reinterpret_cast<uintptr_t>(d_arena) & 255) == 0, "arena too small or unaligned");
@@ -1078,15 +1069,7 @@ int wsis_rulebook_pyramid(const int32_t* d_indices0, int64_t M0, const int32_t* 
   auto at = [&](int l, int f) -> void* { return L.off[l][f] < 0 ? nullptr : A + L.off[l][f]; };
   const int32_t k3[3] = {3, 3, 3}, p1[3] = {1, 1, 1}, k2[3] = {2, 2, 2}, s2[3] = {2, 2, 2}, p0[3] = {0, 0, 0};
   int32_t shape[3] = {h_shape3[0], h_shape3[1], h_shape3[2]};
-  const void* t_idx[16];
-  const void* t_mask[16];
-  int64_t t_M[16];
-  const void* pk_nbr[16];
-  const void* pk_order[16];
-  void* pk_out[16];
-  int64_t pk_M[16];
-  int32_t pk_K[16];
-  int nt = 0;
+  PyrTables T;
   const int32_t* indices = d_indices0;
   for (int l = 0; l < n_levels; ++l) {
     const int64_t M = L.off[l][WSIS_PYR_ROWS], cap = L.off[l][WSIS_PYR_CAP];
@@ -1100,15 +1083,8 @@ int wsis_rulebook_pyramid(const int32_t* d_indices0, int64_t M0, const int32_t* 
     rc = wsis_rulebook_subm(indices, M, shape, k3, p1, keys, vals, cap, static_cast<int32_t*>(at(l, WSIS_PYR_SUBM_NBR)),
                             static_cast<uint32_t*>(at(l, WSIS_PYR_SUBM_MASK)), stream);
     if (rc != WSIS_OK) return rc;
-    t_idx[nt] = indices;
-    t_mask[nt] = at(l, WSIS_PYR_SUBM_MASK);
-    t_M[nt] = M;
-    pk_nbr[nt] = at(l, WSIS_PYR_SUBM_NBR);
-    pk_order[nt] = at(l, WSIS_PYR_SUBM_ORDER);
-    pk_out[nt] = at(l, WSIS_PYR_SUBM_NBR_P);
-    pk_M[nt] = M;
-    pk_K[nt] = 27;
-    ++nt;
+    T.add(indices, M, 27, at(l, WSIS_PYR_SUBM_MASK), at(l, WSIS_PYR_SUBM_NBR), at(l, WSIS_PYR_SUBM_ORDER),
+          at(l, WSIS_PYR_SUBM_NBR_P));
     if (l + 1 == n_levels) break;
     const int64_t M_out = L.off[l + 1][WSIS_PYR_ROWS];
     int32_t out_shape[3];
@@ -1131,48 +1107,21 @@ int wsis_rulebook_pyramid(const int32_t* d_indices0, int64_t M0, const int32_t* 
                                  static_cast<uint32_t*>(at(l, WSIS_PYR_DOWN_MASK)), static_cast<uint32_t*>(at(l, WSIS_PYR_UP_MASK)),
                                  stream);
     if (rc != WSIS_OK) return rc;
-    t_idx[nt] = idx_out;
-    t_mask[nt] = at(l, WSIS_PYR_DOWN_MASK);
-    t_M[nt] = M_out;
-    pk_nbr[nt] = at(l, WSIS_PYR_DOWN_NBR);
-    pk_order[nt] = at(l, WSIS_PYR_DOWN_ORDER);
-    pk_out[nt] = at(l, WSIS_PYR_DOWN_NBR_P);
-    pk_M[nt] = M_out;
-    pk_K[nt] = 8;
-    ++nt;
-    t_idx[nt] = indices;
-    t_mask[nt] = at(l, WSIS_PYR_UP_MASK);
-    t_M[nt] = M;
-    pk_nbr[nt] = at(l, WSIS_PYR_UP_NBR);
-    pk_order[nt] = at(l, WSIS_PYR_UP_ORDER);
-    pk_out[nt] = at(l, WSIS_PYR_UP_NBR_P);
-    pk_M[nt] = M;
-    pk_K[nt] = 8;
-    ++nt;
+    T.add(idx_out, M_out, 8, at(l, WSIS_PYR_DOWN_MASK), at(l, WSIS_PYR_DOWN_NBR), at(l, WSIS_PYR_DOWN_ORDER),
+          at(l, WSIS_PYR_DOWN_NBR_P));
+    T.add(indices, M, 8, at(l, WSIS_PYR_UP_MASK), at(l, WSIS_PYR_UP_NBR), at(l, WSIS_PYR_UP_ORDER),
+          at(l, WSIS_PYR_UP_NBR_P));
     indices = idx_out;
     for (int j = 0; j < 3; ++j) shape[j] = out_shape[j];
   }
-  // all tile orders from one sort, all packed tables from one launch (the tables without rows are skipped inside)
-  {
-    const void* ti[16];
-    const void* tm[16];
-    int64_t tM[16];
-    int n = 0;
-    for (int t = 0; t < nt; ++t)
-      if (t_M[t] > 0) {
-        ti[n] = t_idx[t];
-        tm[n] = t_mask[t];
-        tM[n] = t_M[t];
-        ++n;
-      }
-    // (segments of order_all follow the tables WITH rows only when every table has rows; an empty level breaks the
-    // contiguity assumption of the layout, so such a pyramid takes the per-table path)
-    WSIS_REQUIRE(n == nt, "a level without voxels: use the per-table build");
-    const int rc = wsis_tile_order_batch(n, ti, tm, tM, block_shift, batch_size, reinterpret_cast<int32_t*>(A + L.order_all),
-                                         A + L.tile_ws, L.tile_ws_bytes, stream);
-    if (rc != WSIS_OK) return rc;
-  }
-  return wsis_rulebook_pack_batch(nt, pk_nbr, pk_order, pk_out, pk_M, pk_K, stream);
+  // all tile orders from one sort, all packed tables from one launch
+  // (the segments of order_all follow the layout's tables only when every table has rows; an empty level breaks that
+  // contiguity, so such a pyramid takes the per-table path)
+  WSIS_REQUIRE(T.n_rows == T.n, "a level without voxels: use the per-table build");
+  const int rc = wsis_tile_order_batch(T.n, T.idx, T.mask, T.M, block_shift, batch_size, reinterpret_cast<int32_t*>(A + L.order_all),
+                                       A + L.tile_ws, L.tile_ws_bytes, stream);
+  if (rc != WSIS_OK) return rc;
+  return wsis_rulebook_pack_batch(T.n, T.nbr, T.order, T.out, T.M, T.K, stream);
 }
 
 }  // extern "C"

@@ -65,63 +65,62 @@ def _tile_block_shift():
     return int(os.environ.get("WSIS_TILE_BLOCK_SHIFT", "4"))
 
 
-def _tile_order(indices, mask):
-    """stable sort of the rows by (batch, Morton block, offset mask) -> int32 [M] tile order"""
-    bs = _tile_block_shift()
-    if bs < 0:
-        return _mask_order(mask)
-    M = indices.shape[0]
-    lib = _n.hip()
-    ws_bytes = lib.wsis_tile_order_workspace_bytes(M)
-    if ws_bytes < 0:
-        raise _n.WsisError("tile_order workspace query failed")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=indices.device)
-    order = torch.empty(M, dtype=torch.int32, device=indices.device)
-    _n.check(lib.wsis_tile_order(_n.ptr(indices), _n.ptr(mask), M, bs, _n.ptr(order), _n.ptr(ws), ws_bytes,
-                                 _n.stream_ptr()), "tile_order")
-    return order
-
-
 def _tile_batch_enabled(batch_size):
     """one sort for all tables of a pyramid (WSIS_TILE_BATCH=0: one sort per table)"""
     return (os.environ.get("WSIS_TILE_BATCH", "1") != "0" and _use_mask_order() and _tile_block_shift() >= 0
             and 1 <= int(batch_size) <= 16)
 
 
-def finish_tile_orders(deferred, batch_size):
-    """``deferred``: [(rulebook, "order" | "order_up", indices, mask)] collected while the tables of a pyramid were
-    built without their tile orders.  One ``wsis_tile_order_batch`` call (a single sort with the table number in the
-    top key bits) produces all of them -- the same orders ``_tile_order`` gives table by table -- then every rulebook
-    is packed."""
+def _c_array(ctype, values):
+    return (ctype * len(values))(*values)
+
+
+def finish_tile_orders(tables, batch_size=0):
+    """``tables``: [(rulebook, "order" | "order_up", indices, mask)] registered while the gather tables were built.
+    Sets the tile order of every table and the packed tables (columns in tile order) of every rulebook named there;
+    the one place that decides how:
+
+    * no order (``nbr_p is nbr``): ``WSIS_MASK_ORDER=0``, a table without a mask (K > 32) or without rows;
+    * ``WSIS_TILE_BLOCK_SHIFT < 0``: the plain mask order of each table;
+    * ``_tile_batch_enabled(batch_size)``: up to 16 tables per ``wsis_tile_order_batch`` call (one sort, the table
+      number in the top key bits); otherwise (``WSIS_TILE_BATCH=0``, more than 16 scenes or an unknown batch size)
+      each table alone through ``wsis_tile_order`` -- the same implementation with one table, hence the same orders;
+    * packing: ``wsis_rulebook_pack_batch``, 16 tables per launch."""
     import ctypes
     lib = _n.hip()
-    todo = [d for d in deferred if d[2].shape[0] > 0]
-    rbs = []
-    for d in deferred:
-        if not any(d[0] is r for r in rbs):
-            rbs.append(d[0])
-    for i in range(0, len(todo), 16):
-        part = todo[i:i + 16]
-        n = len(part)
+    bs = _tile_block_shift()
+    todo = [d for d in tables if d[3] is not None and d[2].shape[0] > 0] if _use_mask_order() else []
+    if bs < 0:
+        for rb, name, _, mask in todo:
+            setattr(rb, name, _mask_order(mask))
+        todo = []
+    group = 16 if _tile_batch_enabled(batch_size) else 1
+    for i in range(0, len(todo), group):
+        part = todo[i:i + group]
         Ms = [int(d[2].shape[0]) for d in part]
         N = sum(Ms)
         dev = part[0][2].device
-        ws_bytes = lib.wsis_tile_order_batch_workspace_bytes(N)
+        ws_bytes = lib.wsis_tile_order_workspace_bytes(N)      # (one function of the row total serves both calls)
         if ws_bytes < 0:
-            raise _n.WsisError("tile_order_batch workspace query failed")
+            raise _n.WsisError("tile_order workspace query failed")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         order_all = torch.empty(N, dtype=torch.int32, device=dev)
-        h_ind = (ctypes.c_void_p * n)(*[d[2].data_ptr() for d in part])
-        h_mask = (ctypes.c_void_p * n)(*[d[3].data_ptr() for d in part])
-        h_M = (ctypes.c_int64 * n)(*Ms)
-        _n.check(lib.wsis_tile_order_batch(n, h_ind, h_mask, h_M, _tile_block_shift(), int(batch_size),
-                                           _n.ptr(order_all), _n.ptr(ws), ws_bytes, _n.stream_ptr()),
-                 "tile_order_batch")
+        if len(part) == 1:
+            _n.check(lib.wsis_tile_order(_n.ptr(part[0][2]), _n.ptr(part[0][3]), N, bs, _n.ptr(order_all), _n.ptr(ws),
+                                         ws_bytes, _n.stream_ptr()), "tile_order")
+        else:
+            _n.check(lib.wsis_tile_order_batch(len(part), _c_array(ctypes.c_void_p, [d[2].data_ptr() for d in part]),
+                                               _c_array(ctypes.c_void_p, [d[3].data_ptr() for d in part]),
+                                               _c_array(ctypes.c_int64, Ms), bs, int(batch_size), _n.ptr(order_all),
+                                               _n.ptr(ws), ws_bytes, _n.stream_ptr()), "tile_order_batch")
         off = 0
         for d, M in zip(part, Ms):
             setattr(d[0], d[1], order_all[off:off + M])
             off += M
-    # packed tables (columns in tile order) of every rulebook, 16 tables per launch
+    rbs = []
+    for d in tables:
+        if not any(d[0] is r for r in rbs):
+            rbs.append(d[0])
     jobs = []
     for rb in rbs:
         for nbr, order, name in ((rb.nbr, rb.order, "nbr_p"), (rb.nbr_up, rb.order_up, "nbr_up_p")):
@@ -135,13 +134,12 @@ def finish_tile_orders(deferred, batch_size):
             jobs.append((nbr, order, out))
     for i in range(0, len(jobs), 16):
         part = jobs[i:i + 16]
-        n = len(part)
         _n.check(lib.wsis_rulebook_pack_batch(
-            n, (ctypes.c_void_p * n)(*[j[0].data_ptr() for j in part]),
-            (ctypes.c_void_p * n)(*[j[1].data_ptr() for j in part]),
-            (ctypes.c_void_p * n)(*[j[2].data_ptr() for j in part]),
-            (ctypes.c_int64 * n)(*[int(j[0].shape[1]) for j in part]),
-            (ctypes.c_int32 * n)(*[int(j[0].shape[0]) for j in part]), _n.stream_ptr()), "rulebook_pack_batch")
+            len(part), _c_array(ctypes.c_void_p, [j[0].data_ptr() for j in part]),
+            _c_array(ctypes.c_void_p, [j[1].data_ptr() for j in part]),
+            _c_array(ctypes.c_void_p, [j[2].data_ptr() for j in part]),
+            _c_array(ctypes.c_int64, [int(j[0].shape[1]) for j in part]),
+            _c_array(ctypes.c_int32, [int(j[0].shape[0]) for j in part]), _n.stream_ptr()), "rulebook_pack_batch")
 
 
 def _mask_order(mask):
@@ -155,16 +153,6 @@ def _mask_order(mask):
     _n.check(lib.wsis_mask_order(_n.ptr(mask), M, _n.ptr(order), _n.ptr(ws), ws_bytes, _n.stream_ptr()),
              "mask_order")
     return order
-
-
-def _pack(nbr, order):
-    if order is None or nbr.shape[1] == 0:
-        return nbr
-    K, M = nbr.shape
-    packed = torch.empty_like(nbr)
-    _n.check(_n.hip().wsis_rulebook_pack(_n.ptr(nbr), _n.ptr(order), _n.ptr(packed), M, K, _n.stream_ptr()),
-             "rulebook_pack")
-    return packed
 
 
 class Rulebook(object):
@@ -185,11 +173,6 @@ class Rulebook(object):
         self.nbr_up_p = None
         self.out_hash = None
 
-    def pack(self):
-        self.nbr_p = _pack(self.nbr, self.order)
-        if self.nbr_up is not None:
-            self.nbr_up_p = _pack(self.nbr_up, self.order_up)
-
     # upstream-format export (tests / INTEGRATION.md): indice_pairs int32 [K,2,maxP] (-1 padded),
     # indice_pair_num int32 [K]; pair order inside an offset = ascending output row.
     def to_pairs(self):
@@ -208,7 +191,7 @@ class Rulebook(object):
 
 def build_subm_rulebook(indices, spatial_shape, ksize, padding, hash_tab=None, deferred=None):
     """SubMConv3d rulebook (a5): out rows == in rows, nbr[k][o] = i with coord_i = coord_o - pad + kappa.
-    With ``deferred`` (a list) the tile order and the packed table are left to ``finish_tile_orders``."""
+    With ``deferred`` (a list) the tile order and the packed table are left to the caller's ``finish_tile_orders``."""
     _n.require_cuda(indices)
     _check_indices(indices)
     M = indices.shape[0]
@@ -224,12 +207,10 @@ def build_subm_rulebook(indices, spatial_shape, ksize, padding, hash_tab=None, d
                                          _n.i32x3(padding), _n.ptr(keys), _n.ptr(vals), cap, _n.ptr(rb.nbr),
                                          _n.ptr(mask), _n.stream_ptr()), "rulebook_subm")
     rb.out_hash = hash_tab
-    if deferred is not None and mask is not None and _use_mask_order():
+    if deferred is None:
+        finish_tile_orders([(rb, "order", indices, mask)])
+    else:
         deferred.append((rb, "order", indices, mask))
-        return rb
-    if mask is not None and _use_mask_order() and M > 0:
-        rb.order = _tile_order(indices, mask)
-    rb.pack()
     return rb
 
 
@@ -394,16 +375,11 @@ def _down_rulebook_gen(indices, spatial_shape, ksize, stride, padding, deferred=
                                          _n.ptr(rb.nbr_up), _n.ptr(mask_down), _n.ptr(mask_up), st),
              "rulebook_down_fill")
     rb.out_hash = (keys, vals, cap)
-    if deferred is not None and use_mask and _use_mask_order():
-        deferred.append((rb, "order", out_indices, mask_down))
-        deferred.append((rb, "order_up", indices, mask_up))
-        return rb
-    if use_mask and _use_mask_order():
-        if M_out > 0:
-            rb.order = _tile_order(out_indices, mask_down)
-        if M_in > 0:
-            rb.order_up = _tile_order(indices, mask_up)
-    rb.pack()
+    tables = [(rb, "order", out_indices, mask_down), (rb, "order_up", indices, mask_up)]
+    if deferred is None:
+        finish_tile_orders(tables)
+    else:
+        deferred += tables
     return rb
 
 
@@ -790,7 +766,7 @@ def _build_pyramid_gen(tensor, n_levels, subm_key, down_key, first_id):
     indices, shape = tensor.indices, [int(s) for s in tensor.spatial_shape]
     hash_tab = tensor._hash
     batch_size = int(getattr(tensor, "batch_size", 0) or 0)
-    deferred = [] if _tile_batch_enabled(batch_size) else None
+    deferred = []
     new_rbs = []
     hints = getattr(tensor, "_level_counts", None)
     if hints is not None and (len(hints) != n_levels - 1 or os.environ.get("WSIS_LEVEL_COUNTS", "1") == "0"):
@@ -831,8 +807,7 @@ def _build_pyramid_gen(tensor, n_levels, subm_key, down_key, first_id):
                 tensor.indice_dict[dkey] = rb
                 new_rbs.append(rb)
             indices, shape, hash_tab = rb.out_indices, rb.out_shape, rb.out_hash
-    if deferred:
-        finish_tile_orders(deferred, batch_size)
+    finish_tile_orders(deferred, batch_size)
     for rb in new_rbs:
         built += _rulebook_tensors(rb)
     return built

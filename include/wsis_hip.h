@@ -149,8 +149,10 @@ int wsis_rulebook_down_fill(const int32_t* d_indices_in, int64_t M_in, const int
  * same set of active offsets become neighbours so whole tiles skip inactive offsets). */
 int64_t wsis_mask_order_workspace_bytes(int64_t M);
 /* Spatial + mask tile ordering: stable sort by (batch, Morton code of the row's block of 2^block_shift voxels
- * per side, offset mask).  Rows of one block become neighbours, so the gathers of a tile hit the same L1/L2
- * lines; inside a block equal offset sets stay adjacent.  d_mask may be NULL (pure spatial order). */
+ * per side, offset mask), then the full 32-row slices heaviest first.  Rows of one block become neighbours, so the
+ * gathers of a tile hit the same L1/L2 lines; inside a block equal offset sets stay adjacent.  d_mask may be NULL
+ * (pure spatial order).  This is the one-table call of the implementation behind wsis_tile_order_batch: the key
+ * has no table number and keeps 8 bits of the batch index (batches of up to 256 scenes). */
 int64_t wsis_tile_order_workspace_bytes(int64_t M);
 int wsis_tile_order(const int32_t* d_indices, const uint32_t* d_mask, int64_t M, int32_t block_shift,
                     int32_t* d_order, void* d_ws, int64_t ws_bytes, void* stream);
@@ -158,9 +160,10 @@ int wsis_mask_order(const uint32_t* d_mask, int64_t M, int32_t* d_order, void* d
                     void* stream);
 /* The tile orders of up to 16 gather tables (every table of a UNet pyramid) from ONE sort: h_indices[t] /
  * h_mask[t] are host arrays of device pointers (int32 [M_t,4] / uint32 [M_t] or NULL), h_M the row counts.
- * d_order_all int32 [sum M_t]: table t's order (row numbers local to the table, identical to what
- * wsis_tile_order returns for it) at offset sum_{u<t} M_u.  The batch index of every row must be < 16
- * (batch_size, checked on the host side); N = sum M_t for the workspace query. */
+ * d_order_all int32 [sum M_t]: table t's order (row numbers local to the table, what wsis_tile_order returns
+ * for it) at offset sum_{u<t} M_u.  The key carries the table number in its top 4 bits and 4 bits of the batch
+ * index below them: the batch index of every row must be < 16 (batch_size, checked on the host side).
+ * N = sum M_t for the workspace query; the two workspace queries are one function of the row total. */
 int64_t wsis_tile_order_batch_workspace_bytes(int64_t N);
 int wsis_tile_order_batch(int32_t n, const void* const* h_indices, const void* const* h_mask, const int64_t* h_M,
                           int32_t block_shift, int32_t batch_size, int32_t* d_order_all, void* d_ws,
@@ -171,7 +174,8 @@ int wsis_tile_order_batch(int32_t n, const void* const* h_indices, const void* c
  * unpacked table as is. */
 int wsis_rulebook_pack(const int32_t* d_nbr, const int32_t* d_order, int32_t* d_nbr_packed, int64_t M,
                        int32_t K, void* stream);
-/* the same for up to 16 tables in one launch: host arrays of device pointers / sizes, one entry per table */
+/* the same for up to 16 tables in one launch: host arrays of device pointers / sizes, one entry per table
+ * (wsis_rulebook_pack is this launch with one table) */
 int wsis_rulebook_pack_batch(int32_t n, const void* const* h_nbr, const void* const* h_order,
                              void* const* h_nbr_packed, const int64_t* h_M, const int32_t* h_K, void* stream);
 
