@@ -16,6 +16,8 @@ import os
 import numpy as np
 import torch
 
+from wsis_datasets import SceneRecord, assemble_batch, instance_slots, voxelize_and_count
+
 SCALE = 50            # config/ScanNet_v2_3D_WSIS.yaml:31 (2 cm voxels)
 FULL_SCALE_MIN = 128  # :30 full_scale[0]
 
@@ -178,80 +180,33 @@ def synthetic_predictions(scene, seed=0, noise=0.02):
 
 
 # -------------------------------------------------------------------------------------------------------------
+def _scene_record(sc, i):
+    """``make_scene`` dict -> record: voxel coordinates = floor(xyz * 50) from the scene's minimum"""
+    v = np.floor(sc["xyz"].astype(np.float64) * SCALE).astype(np.int64)
+    return SceneRecord(
+        name=f"synthetic_{i}", loc=torch.from_numpy(v - v.min(0)), loc_float=torch.from_numpy(sc["xyz"]).float(),
+        feat=torch.from_numpy(sc["rgb"]).float(), sem=torch.from_numpy(sc["sem_label"]).long(),
+        ins=torch.from_numpy(sc["ins_label"]).long(), sp=torch.from_numpy(sc["superpoint"]).long(), S=sc["S"],
+        n_inst=sc["n_inst"], sp_sem=torch.from_numpy(sc["sp_sem"]).long(), sp_ins=torch.from_numpy(sc["sp_ins"]).long(),
+        sp_off=torch.from_numpy(sc["sp_offset"]).float(), sp_size=torch.from_numpy(sc["sp_size"]).float(),
+        sp_vox=torch.from_numpy(sc["sp_voxnum"]).float(), edges=torch.from_numpy(sc["edges"]).long(),
+        edge_feats=torch.from_numpy(sc["edge_feats"]).float())
+
+
 def _assemble_host(scenes):
     """everything of ``collate_fn`` (scannetv2_dataset.py:343-474) that is plain concatenation: per-point and
     per-superpoint arrays with batch / superpoint / instance offsets, the two edge orders, the ECC graph -- no hashing"""
-    from graphnet import GraphConvInfo
-    locs, locs_float, feats, sem, ins, sps = [], [], [], [], [], []
-    sp_sem, sp_ins, sp_off, sp_vox, sp_size = [], [], [], [], []
-    edge_sorted, edge_feats_sorted, edges_ext = [], [], []
-    batch_offsets, sp_batch_offsets = [0], [0]
-    sp_bias, inst_bias = 0, 0
-    for b, sc in enumerate(scenes):
-        xyz = sc["xyz"]
-        v = np.floor(xyz.astype(np.float64) * SCALE).astype(np.int64)
-        v = v - v.min(0)
-        locs.append(torch.cat([torch.full((len(v), 1), b, dtype=torch.int64), torch.from_numpy(v)], 1))
-        locs_float.append(torch.from_numpy(xyz))
-        feats.append(torch.from_numpy(sc["rgb"]))
-        sem.append(torch.from_numpy(sc["sem_label"]))
-        il = sc["ins_label"].copy()
-        il[il != -100] += inst_bias
-        ins.append(torch.from_numpy(il))
-        sps.append(torch.from_numpy(sc["superpoint"] + sp_bias))
-        sp_sem.append(torch.from_numpy(sc["sp_sem"]))
-        si = sc["sp_ins"].copy()
-        si[si != -100] += inst_bias
-        sp_ins.append(torch.from_numpy(si))
-        sp_off.append(torch.from_numpy(sc["sp_offset"]))
-        sp_vox.append(torch.from_numpy(sc["sp_voxnum"]))
-        sp_size.append(torch.from_numpy(sc["sp_size"]))
-        E = sc["edges"]
-        order = np.argsort(E[:, 1], kind="stable")          # ecc/GraphConvInfo.py:54 (sorted by target)
-        edge_sorted.append(torch.from_numpy(E[order] + sp_bias))
-        edge_feats_sorted.append(torch.from_numpy(sc["edge_feats"][order]))
-        edges_ext.append(torch.from_numpy(E + sp_bias))     # original (sorted-tuple) order, :455-457
-        sp_bias += sc["S"]
-        inst_bias += sc["n_inst"]
-        batch_offsets.append(batch_offsets[-1] + len(v))
-        sp_batch_offsets.append(sp_bias)
-    locs = torch.cat(locs, 0)
-    spatial_shape = np.clip((locs.max(0)[0][1:] + 1).numpy(), FULL_SCALE_MIN, None)
-    edge_indexes = torch.cat(edge_sorted, 0).t().contiguous()
-    GIs = [GraphConvInfo(edge_indexes, torch.cat(edge_feats_sorted, 0), sp_bias)]
-    edges = torch.cat(edges_ext, 0)
-    return {
-        "locs": locs,
-        "locs_float": torch.cat(locs_float, 0).float(), "feats": torch.cat(feats, 0).float(),
-        "semantic_labels": torch.cat(sem, 0).long(), "instance_labels": torch.cat(ins, 0).long(),
-        "offsets": torch.tensor(batch_offsets, dtype=torch.int32), "spatial_shape": spatial_shape,
-        "superpoint": torch.cat(sps, 0).long(), "GIs": GIs,
-        "sp_batch_offsets": torch.tensor(sp_batch_offsets, dtype=torch.int32),
-        "edge_u_list": edges[:, 0].contiguous().long(), "edge_v_list": edges[:, 1].contiguous().long(),
-        # rows of scatter(..., edge_u): known here on the host, so the device step never has to read it back
-        "edge_src_rows": (int(edges[:, 0].max()) + 1) if edges.shape[0] else 0,
-        "superpoint_semantic_labels": torch.cat(sp_sem, 0).long(),
-        "superpoint_instance_labels": torch.cat(sp_ins, 0).long(),
-        "superpoint_offset_vector": torch.cat(sp_off, 0).float(),
-        # (torch's CPU log, as the reference's collate_fn, scannetv2_dataset.py:438: numpy's differs in the last bit)
-        "superpoint_instance_voxel_num": torch.log(torch.cat(sp_vox, 0).float()),
-        "superpoint_instance_size": torch.cat(sp_size, 0).float(),
-        "scene_list": [f"synthetic_{i}" for i in range(len(scenes))],
-    }
+    out = assemble_batch([_scene_record(sc, i) for i, sc in enumerate(scenes)], shift_sp_instances=True,
+                         full_scale_min=FULL_SCALE_MIN)
+    del out["sp_instance_slots"]     # (a host dict may still be edited: ``to_device`` takes them from the labels it uploads)
+    return out
 
 
 def collate(scenes, mode=4, n_levels=5):
     """Batch dict with the schema of scannetv2_dataset.py:460-474; host tensors: the voxel hash runs on
     ONE host thread (libwsis_host.so), as in the reference's DataLoader workers (:445-449).
     ``n_levels``: UNet depth the host-side ``level_counts`` are computed for (config ``blocks``)."""
-    import pointgroup_ops
-    import spconv
-    out = _assemble_host(scenes)
-    voxel_locs, p2v_map, v2p_map = pointgroup_ops.voxelization_idx(out["locs"], len(scenes), mode)
-    out.update(voxel_locs=voxel_locs, p2v_map=p2v_map, v2p_map=v2p_map)
-    # active voxels of the UNet's strided levels, from the host-side coordinates (spconv.ops.level_voxel_counts)
-    out["level_counts"] = spconv.ops.level_voxel_counts(voxel_locs.numpy(), out["spatial_shape"], n_levels)
-    return out
+    return voxelize_and_count(_assemble_host(scenes), len(scenes), mode, n_levels)
 
 
 def collate_device(scenes, device, mode=4, n_levels=5):
@@ -260,14 +215,11 @@ def collate_device(scenes, device, mode=4, n_levels=5):
     contract) builds voxel_locs / p2v / v2p and the pyramid's level counts come from one sort per level -- two small
     read-backs in this loader stage (voxel count + list width, then the level counts), none in the training step.
     Returns what ``to_device(collate(scenes))`` returns."""
-    import pointgroup_ops
-    import spconv
     host = _assemble_host(scenes)
-    locs_d = host["locs"].to(device, non_blocking=True)
-    voxel_locs, p2v_map, v2p_map = pointgroup_ops.voxelization_idx(locs_d, len(scenes), mode)
-    counts = spconv.ops.level_voxel_counts_device(voxel_locs, host["spatial_shape"], n_levels)
-    host.update(voxel_locs=voxel_locs, p2v_map=p2v_map, v2p_map=v2p_map)
-    host["level_counts"] = [int(v) for v in counts.tolist()]
+    locs = host["locs"]
+    host["locs"] = locs.to(device, non_blocking=True)
+    voxelize_and_count(host, len(scenes), mode, n_levels)
+    host["locs"] = locs                  # (``locs`` itself stays the host tensor it is behind ``to_device(collate(...))``)
     return to_device(host, device)
 
 
@@ -315,90 +267,33 @@ def pack_scene(sc, pin=True, buf=None):
 _TORCH_DT = {np.float32: torch.float32, np.int64: torch.int64}
 
 
+def _packed_record(pk, dev, i):
+    """``pack_scene`` pack -> record on ``dev``: one H2D copy of the buffer, every field a view of it"""
+    d = pk["buf"].to(dev, non_blocking=True)
+
+    def f(name):
+        off, shape, dt = pk["layout"][name]
+        n = int(np.prod(shape)) * np.dtype(dt).itemsize
+        return d[off:off + n].view(_TORCH_DT[dt]).view(shape)
+    xyz = f("xyz")
+    return SceneRecord(
+        name=f"synthetic_{i}", loc=torch.floor(xyz.double() * SCALE).long() - f("vmin"), loc_float=xyz, feat=f("rgb"),
+        sem=f("sem_label"), ins=f("ins_label"), sp=f("superpoint"), S=pk["S"], n_inst=pk["n_inst"], sp_sem=f("sp_sem"),
+        sp_ins=f("sp_ins"), sp_off=f("sp_offset"), sp_size=f("sp_size"), sp_vox=f("sp_voxnum"), sp_vox_is_log=True,
+        edges=f("edges"), edge_feats=f("edge_feats"), extent=pk["extent"], edge_src_max=pk["edge_src_max"],
+        sp_ins_max=pk["sp_ins_max"])
+
+
 def collate_packed(packs, device, mode=4, n_levels=5):
     """Batch of packed scenes (``pack_scene``) assembled ON THE DEVICE: per scene one H2D copy of its pinned buffer; the
     concatenations, batch / superpoint / instance offsets (scannetv2_dataset.py:383-396), the target-sorted edge order of
     the ECC graph (ecc/GraphConvInfo.py:54), voxel hash and pyramid counts all run there.  The host thread only lays out
     the batch from the packs' counts (a few dozen Python statements per scene).  Returns what
     ``to_device(collate(scenes))`` returns."""
-    import pointgroup_ops
-    import spconv
-    from graphnet import GraphConvInfo
     dev = torch.device(device)
-    cols = {k: [] for k in ("locs", "locs_float", "feats", "sem", "ins", "sps", "sp_sem", "sp_ins", "sp_off", "sp_vox",
-                            "sp_size", "edge_sorted", "edge_feats_sorted", "edges_ext")}
-    batch_offsets, sp_batch_offsets = [0], [0]
-    sp_bias, inst_bias = 0, 0
-    extent = np.zeros(3, dtype=np.int64)
-    edge_src_rows, slots = 0, []
-    for b, pk in enumerate(packs):
-        d = pk["buf"].to(dev, non_blocking=True)
-
-        def f(name):
-            off, shape, dt = pk["layout"][name]
-            n = int(np.prod(shape)) * np.dtype(dt).itemsize
-            return d[off:off + n].view(_TORCH_DT[dt]).view(shape)
-        xyz = f("xyz")
-        v = torch.floor(xyz.double() * SCALE).long() - f("vmin")
-        cols["locs"].append(torch.cat([torch.full((pk["N"], 1), b, dtype=torch.int64, device=dev), v], 1))
-        cols["locs_float"].append(xyz)
-        cols["feats"].append(f("rgb"))
-        cols["sem"].append(f("sem_label"))
-        il, si = f("ins_label"), f("sp_ins")
-        cols["ins"].append(torch.where(il != -100, il + inst_bias, il) if inst_bias else il)
-        cols["sp_ins"].append(torch.where(si != -100, si + inst_bias, si) if inst_bias else si)
-        cols["sps"].append(f("superpoint") + sp_bias if sp_bias else f("superpoint"))
-        cols["sp_sem"].append(f("sp_sem"))
-        cols["sp_off"].append(f("sp_offset"))
-        cols["sp_vox"].append(f("sp_voxnum"))
-        cols["sp_size"].append(f("sp_size"))
-        E = f("edges")
-        order = torch.argsort(E[:, 1], stable=True)
-        Eb = E + sp_bias if sp_bias else E
-        cols["edge_sorted"].append(Eb[order])
-        cols["edge_feats_sorted"].append(f("edge_feats")[order])
-        cols["edges_ext"].append(Eb)
-        if pk["edge_src_max"] >= 0:
-            edge_src_rows = max(edge_src_rows, pk["edge_src_max"] + sp_bias + 1)
-        # bound of the (batch-offset) instance ids of the scene's superpoints: to_device reads it from the label tensor
-        slots.append(pk["sp_ins_max"] + inst_bias + 1 if pk["sp_ins_max"] >= 0 else 1)
-        extent = np.maximum(extent, pk["extent"])
-        sp_bias += pk["S"]
-        inst_bias += pk["n_inst"]
-        batch_offsets.append(batch_offsets[-1] + pk["N"])
-        sp_batch_offsets.append(sp_bias)
-
-    def cat(k):
-        return cols[k][0] if len(cols[k]) == 1 else torch.cat(cols[k], 0)
-    locs = cat("locs").contiguous()
-    edges = cat("edges_ext")
-    out = {
-        "locs": locs, "locs_float": cat("locs_float").contiguous(), "feats": cat("feats").contiguous(),
-        "semantic_labels": cat("sem").contiguous(), "instance_labels": cat("ins").contiguous(),
-        "offsets": torch.tensor(batch_offsets, dtype=torch.int32),
-        "spatial_shape": np.clip(extent, FULL_SCALE_MIN, None),
-        "superpoint": cat("sps").contiguous(),
-        "GIs": [GraphConvInfo(cat("edge_sorted").t().contiguous(), cat("edge_feats_sorted").contiguous(), sp_bias)],
-        "sp_batch_offsets": torch.tensor(sp_batch_offsets, dtype=torch.int32),
-        "edge_u_list": edges[:, 0].contiguous(), "edge_v_list": edges[:, 1].contiguous(),
-        "edge_src_rows": edge_src_rows,
-        "superpoint_semantic_labels": cat("sp_sem").contiguous(), "superpoint_instance_labels": cat("sp_ins").contiguous(),
-        "superpoint_offset_vector": cat("sp_off").contiguous(),
-        "superpoint_instance_voxel_num": cat("sp_vox").contiguous(),
-        "superpoint_instance_size": cat("sp_size").contiguous(),
-        "scene_list": [f"synthetic_{i}" for i in range(len(packs))],
-        "sp_instance_slots": slots,
-    }
-    voxel_locs, p2v_map, v2p_map = pointgroup_ops.voxelization_idx(locs, len(packs), mode)
-    counts = spconv.ops.level_voxel_counts_device(voxel_locs, out["spatial_shape"], n_levels)
-    out.update(voxel_locs=voxel_locs, p2v_map=p2v_map, v2p_map=v2p_map)
-    out["level_counts"] = [int(c) for c in counts.tolist()]
-    out["voxel_coords_int"] = voxel_locs.int().contiguous()
-    ev = torch.cuda.Event()
-    ev.record()
-    out["coords_ready_event"] = ev
-    build_batch_graphs(out)
-    return out
+    out = assemble_batch([_packed_record(pk, dev, i) for i, pk in enumerate(packs)], shift_sp_instances=True,
+                         full_scale_min=FULL_SCALE_MIN)
+    return finish_device_batch(voxelize_and_count(out, len(packs), mode, n_levels))
 
 
 _DEVICE_KEYS = ("voxel_locs", "p2v_map", "v2p_map", "locs_float", "feats", "semantic_labels", "instance_labels",
@@ -413,17 +308,23 @@ def to_device(batch, device):
     out = dict(batch)
     for k in _DEVICE_KEYS:
         out[k] = batch[k].to(device)          # (tensors a device-side collate already left on the GPU stay put)
-    out["voxel_coords_int"] = out["voxel_locs"].int().contiguous()
     out["GIs"][0].cuda()
-    ev = torch.cuda.Event()                # every index tensor of the batch is on the device behind this point
+    if "sp_instance_slots" not in out:
+        # read while the labels are still host tensors
+        lab, offs = batch["superpoint_instance_labels"], [int(o) for o in batch["sp_batch_offsets"]]
+        out["sp_instance_slots"] = instance_slots(int(lab[b:e].max()) if e > b else -100
+                                                  for b, e in zip(offs[:-1], offs[1:]))
+    return finish_device_batch(out)
+
+
+def finish_device_batch(batch):
+    """what every batch on the device ends with: the int32 voxel coordinates, the event behind which every index tensor
+    of the batch is on the device, and the per-batch graph structures"""
+    batch["voxel_coords_int"] = batch["voxel_locs"].int().contiguous()
+    ev = torch.cuda.Event()
     ev.record()
-    out["coords_ready_event"] = ev
-    build_batch_graphs(out)
-    # bound of the superpoint instance ids per scene, read while the labels are still host tensors: lets the loss
-    # place the instances in fixed slots instead of torch.unique (sync) or an [S, S] same-instance matrix
-    lab, offs = batch["superpoint_instance_labels"], [int(o) for o in batch["sp_batch_offsets"]]
-    out["sp_instance_slots"] = [max(int(lab[b:e].max()) + 1, 1) if e > b else 1 for b, e in zip(offs[:-1], offs[1:])]
-    return out
+    batch["coords_ready_event"] = ev
+    return build_batch_graphs(batch)
 
 
 def build_batch_graphs(batch, side_stream=None):

@@ -3,9 +3,11 @@
 Mirrors ``modules/datasets/scannetv2_dataset.py`` -- ``__getitem__`` (:96-190), ``data_aug_with_graph`` (:194-209),
 ``elastic`` (:225-250), ``crop`` (:252-273), ``get_instance_info`` (:275-309), ``get_cropped_inst_label`` (:311-330)
 and ``collate_fn`` (:343-474, schema in SURVEY App. C) -- on plain numpy arrays.  Pure host code, safe in DataLoader
-workers (``pointgroup_ops.voxelization_idx`` runs in ``libwsis_host.so``).  The last part of the file is the same
-preparation on the device (``DeviceScenePrep``, ``collate_prepared``: csrc/sceneprep.hip) for scenes
-that stay resident in device memory; it is the only part that touches the GPU.
+workers (``pointgroup_ops.voxelization_idx`` runs in ``libwsis_host.so``).  The layout of the batch dict is written once
+(``SceneRecord``, ``assemble_batch``, ``voxelize_and_count``: the same torch calls wherever the records live; also behind
+``harness.collate*``).  The last part of the file is the same preparation on the device (``DeviceScenePrep``,
+``collate_prepared``: csrc/sceneprep.hip) for scenes that stay resident in device memory; only that part
+and batches of device records touch the GPU.
 
 Two deliberate differences:
 
@@ -356,81 +358,166 @@ class ScenePrep(object):
                 torch.from_numpy(infos["instance_info"]), infos["instance_pointnum"])
 
 
-def _level_counts(voxel_locs, spatial_shape, n_levels=5):
-    """host-side voxel counts of the UNet's strided levels (config ``blocks`` = 5); the device rulebook build sizes
-    its tables from them instead of reading the counts back (spconv.ops.level_voxel_counts)"""
+# ---- batch assembly: ONE layout rule behind the four collate functions ------------------------------
+class SceneRecord(object):
+    """What every input of a collate reduces to: one scene as torch tensors in their final dtypes, on any device.
+
+    ``name``; points ``loc`` int64 [n,3], ``loc_float`` fp32 [n,3], ``feat`` fp32 [n,C], ``sem`` / ``ins`` / ``sp`` int64 [n]
+    (``ins`` and ``sp`` scene-local, -100 = no instance); host ints ``S`` and ``n_inst``; superpoints ``sp_sem`` / ``sp_ins``
+    int64 [S], ``sp_off`` fp32 [S,3], ``sp_size`` / ``sp_vox`` fp32 [S] (``sp_vox_is_log``: the log is taken already);
+    graph ``edges`` int64 [E,2] scene-local in their original order, ``edge_feats`` fp32 [E,13].  The dataset ends add
+    ``loc_offset``, ``inst_info``, ``inst_pointnum``, ``is1ins``.  ``extent`` (int64 [3], loc.max + 1), ``edge_src_max``
+    (-1 without edges) and ``sp_ins_max`` (-100 without superpoints) are the numbers the layout needs on the host."""
+    loc_offset = inst_info = inst_pointnum = is1ins = None
+    extent = edge_src_max = sp_ins_max = None
+    sp_vox_is_log = False
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def host_numbers(self):
+        """(extent, edge_src_max, sp_ins_max) as carried, else read from the tensors -- host tensors only: a record on
+        the device must carry them, so that laying a batch out never reads the device back"""
+        if self.extent is not None and self.edge_src_max is not None and self.sp_ins_max is not None:
+            return self.extent, self.edge_src_max, self.sp_ins_max
+        assert not self.loc.is_cuda, "a scene record on the device must carry extent, edge_src_max and sp_ins_max"
+        return ((self.loc.max(0)[0] + 1).numpy() if self.loc.shape[0] else np.zeros(3, dtype=np.int64),
+                int(self.edges[:, 0].max()) if self.edges.shape[0] else -1,
+                int(self.sp_ins.max()) if self.S else -100)
+
+
+def instance_slots(label_maxima):
+    """``sp_instance_slots``: per scene the bound of the superpoint instance ids AS THE BATCH EMITS THEM (largest label
+    + 1, at least 1) -- lets the loss place the instances in fixed slots instead of torch.unique (a sync) or an [S, S]
+    same-instance matrix"""
+    return [max(int(m) + 1, 1) for m in label_maxima]
+
+
+def assemble_batch(records, *, shift_sp_instances, full_scale_min):
+    """The layout rule of ``collate_fn`` (:343-474), once: batch column, point / superpoint / instance offsets
+    (:383-396), both edge orders (:455-457 and ecc/GraphConvInfo.py:54), the host-side numbers -- everything of the batch
+    dict before the voxel hash, with the same torch calls on whatever device the records live on.
+
+    ``shift_sp_instances``: the reference batches the graph's per-superpoint instance ids as they are (:407; the loss
+    only compares them inside one scene), the dataset ends pass False; the synthetic-workload ends shift them per scene
+    like the point ids and pass True.  ``sp_instance_slots`` follows the labels as emitted either way.
+
+    The inputs are never written to.  A host batch is a copy of them; on the device a bias of 0 adds nothing and a
+    one-scene batch is not concatenated."""
+    from graphnet import GraphConvInfo
+    cols = {k: [] for k in ("locs", "locs_float", "feats", "sem", "ins", "sps", "sp_sem", "sp_ins", "sp_off", "sp_vox",
+                            "sp_size", "edge_sorted", "edge_feats_sorted", "edges_ext", "info", "pointnum", "is1ins")}
+    batch_offsets, sp_batch_offsets, label_maxima = [0], [0], []
+    sp_bias, inst_bias, edge_src_rows = 0, 0, 0
+    extent = np.zeros(3, dtype=np.int64)
+    for b, r in enumerate(records):
+        r_extent, src_max, ins_max = r.host_numbers()
+
+        def shifted(ids):                                          # :389-391, out of place
+            return torch.where(ids != -100, ids + inst_bias, ids) if inst_bias else ids
+        n = r.loc.shape[0]
+        cols["locs"].append(torch.cat([torch.full((n, 1), b, dtype=torch.int64, device=r.loc.device), r.loc], 1))
+        cols["locs_float"].append(r.loc_float)
+        cols["feats"].append(r.feat)
+        cols["sem"].append(r.sem)
+        cols["ins"].append(shifted(r.ins))
+        cols["sps"].append(r.sp + sp_bias if sp_bias else r.sp)
+        cols["sp_sem"].append(r.sp_sem)
+        cols["sp_ins"].append(shifted(r.sp_ins) if shift_sp_instances else r.sp_ins)
+        cols["sp_off"].append(r.sp_off)
+        cols["sp_vox"].append(r.sp_vox)
+        cols["sp_size"].append(r.sp_size)
+        order = torch.argsort(r.edges[:, 1], stable=True)          # ecc/GraphConvInfo.py:54-70 (sorted by target)
+        Eb = r.edges + sp_bias if sp_bias else r.edges
+        cols["edge_sorted"].append(Eb[order])
+        cols["edge_feats_sorted"].append(r.edge_feats[order])
+        cols["edges_ext"].append(Eb)                               # original (sorted-tuple) order, :455-457
+        cols["info"].append(r.inst_info)
+        cols["pointnum"].append(r.inst_pointnum)
+        cols["is1ins"].append(r.is1ins)
+        if src_max >= 0:
+            edge_src_rows = max(edge_src_rows, src_max + sp_bias + 1)
+        label_maxima.append(ins_max + inst_bias if shift_sp_instances and ins_max >= 0 else ins_max)
+        extent = np.maximum(extent, r_extent)
+        sp_bias += r.S
+        inst_bias += r.n_inst
+        batch_offsets.append(batch_offsets[-1] + n)
+        sp_batch_offsets.append(sp_bias)
+    first = records[0]
+
+    def cat(k):
+        c = cols[k]
+        return (c[0] if len(c) == 1 and c[0].is_cuda else torch.cat(c, 0)).contiguous()
+    edges = cat("edges_ext")
+    vox = cat("sp_vox")
+    if not first.sp_vox_is_log:
+        # torch's CPU log, as :438 takes it -- never the device's: it differs in the last bit
+        assert not vox.is_cuda, "a scene record on the device carries the log of its voxel counts"
+        vox = torch.log(vox)
+    out = {
+        "locs": cat("locs"), "locs_float": cat("locs_float"), "feats": cat("feats"), "semantic_labels": cat("sem"),
+        "instance_labels": cat("ins"), "offsets": torch.tensor(batch_offsets, dtype=torch.int32),
+        "spatial_shape": np.clip(extent, full_scale_min, None), "superpoint": cat("sps"),
+        "GIs": [GraphConvInfo(cat("edge_sorted").t().contiguous(), cat("edge_feats_sorted"), sp_bias)],
+        "sp_batch_offsets": torch.tensor(sp_batch_offsets, dtype=torch.int32),
+        "edge_u_list": edges[:, 0].contiguous(), "edge_v_list": edges[:, 1].contiguous(),
+        # rows of scatter(..., edge_u): known here on the host, so the device step never has to read it back
+        "edge_src_rows": edge_src_rows,
+        "superpoint_semantic_labels": cat("sp_sem"), "superpoint_instance_labels": cat("sp_ins"),
+        "superpoint_offset_vector": cat("sp_off"), "superpoint_instance_voxel_num": vox,
+        "superpoint_instance_size": cat("sp_size"), "scene_list": [r.name for r in records],
+        "sp_instance_slots": instance_slots(label_maxima),
+    }
+    if first.loc_offset is not None:
+        out["locs_offset"] = torch.stack([r.loc_offset for r in records])
+    for key, k in (("instance_info", "info"), ("instance_pointnum", "pointnum"), ("is1ins_labels", "is1ins")):
+        if cols[k][0] is not None:
+            out[key] = cat(k)
+    return out
+
+
+def voxelize_and_count(batch, n_scenes, mode, n_levels):
+    """the voxel hash of ``batch["locs"]`` (:445-449) and the active voxels of the UNet's strided levels, on the host or
+    on the device, wherever ``locs`` is; the device rulebook build sizes its tables from the counts instead of reading
+    them back (spconv.ops.level_voxel_counts).  Device: one read-back, of the counts."""
+    import pointgroup_ops
     import spconv
-    return spconv.ops.level_voxel_counts(voxel_locs.numpy(), spatial_shape, n_levels)
+    voxel_locs, p2v_map, v2p_map = pointgroup_ops.voxelization_idx(batch["locs"], n_scenes, mode)
+    if voxel_locs.is_cuda:
+        counts = spconv.ops.level_voxel_counts_device(voxel_locs, batch["spatial_shape"], n_levels)
+        counts = [int(c) for c in counts.tolist()]
+    else:
+        counts = spconv.ops.level_voxel_counts(voxel_locs.numpy(), batch["spatial_shape"], n_levels)
+    batch.update(voxel_locs=voxel_locs, p2v_map=p2v_map, v2p_map=v2p_map, level_counts=counts)
+    return batch
+
+
+def _tuple_record(data):
+    """``ScenePrep`` 12-tuple -> record; the scene has as many superpoints as its largest id says (:385)"""
+    scene, loc, loc_offset, loc_float, feat, sem, ins, superpoint, graph, inst_num, inst_info, inst_pointnum = data
+    vs = graph.vs
+    return SceneRecord(
+        name=scene, loc=loc.long(), loc_float=loc_float.to(torch.float32), feat=feat.to(torch.float32), sem=sem.long(),
+        ins=ins.long(), sp=superpoint.long(), S=int(superpoint.max()) + 1, n_inst=inst_num,
+        sp_sem=torch.as_tensor(vs["semantic_label"]).long(), sp_ins=torch.as_tensor(vs["instance_label"]).long(),
+        sp_off=torch.as_tensor(vs["superpoint_offset_vector"]).to(torch.float32),
+        sp_size=torch.as_tensor(vs["instance_size"]).to(torch.float32),
+        sp_vox=torch.as_tensor(vs["instance_voxel_num"]).to(torch.float32),
+        edges=torch.from_numpy(graph.edges), edge_feats=torch.from_numpy(graph.f).float(),
+        loc_offset=loc_offset, inst_info=inst_info.to(torch.float32),
+        inst_pointnum=torch.tensor(inst_pointnum, dtype=torch.int), is1ins=torch.from_numpy(graph.is1ins))
 
 
 def collate_fn(batch, full_scale_min=128, mode=4):
     """``collate_fn`` (:343-474): list of ``ScenePrep`` 12-tuples -> batch dict."""
-    import pointgroup_ops
-    from graphnet import GraphConvInfo
-    locs, loc_offsets, locs_float, feats, sems, inss, sps = [], [], [], [], [], [], []
-    infos, pointnum, scene_list = [], [], []
-    sp_sem, sp_ins, sp_off, sp_vox, sp_size = [], [], [], [], []
-    edge_sorted, feat_sorted, edges_ext, is1ins = [], [], [], []
-    batch_offsets, sp_batch_offsets = [0], [0]
-    sp_bias, total_inst = 0, 0
-    for i, data in enumerate(batch):
-        scene, loc, loc_offset, loc_float, feat, sem, ins, superpoint, graph, inst_num, inst_info, inst_pointnum = data
-        scene_list.append(scene)
-        superpoint = superpoint + sp_bias
-        this_bias = sp_bias
-        sp_bias = int(superpoint.max()) + 1
-        sp_batch_offsets.append(sp_bias)
-        ins = ins.clone()
-        ins[ins != -100] += total_inst
-        total_inst += inst_num
-        batch_offsets.append(batch_offsets[-1] + loc.shape[0])
-        locs.append(torch.cat([torch.full((loc.shape[0], 1), i, dtype=torch.int64), loc], 1))
-        loc_offsets.append(loc_offset)
-        locs_float.append(loc_float)
-        feats.append(feat)
-        sems.append(sem)
-        inss.append(ins)
-        sps.append(superpoint)
-        sp_sem.append(torch.as_tensor(graph.vs["semantic_label"]))
-        sp_ins.append(torch.as_tensor(graph.vs["instance_label"]))
-        sp_off.append(torch.as_tensor(graph.vs["superpoint_offset_vector"]))
-        sp_vox.append(torch.as_tensor(graph.vs["instance_voxel_num"]))
-        sp_size.append(torch.as_tensor(graph.vs["instance_size"]))
-        infos.append(inst_info)
-        pointnum.extend(inst_pointnum)
-        E = graph.edges
-        order = np.argsort(E[:, 1], kind="stable")                 # ecc/GraphConvInfo.py:54-70 (sorted by target)
-        edge_sorted.append(torch.from_numpy(E[order] + this_bias))
-        feat_sorted.append(torch.from_numpy(graph.f[order]))
-        edges_ext.append(torch.from_numpy(E + this_bias))          # original order (:455-457)
-        is1ins.append(torch.from_numpy(graph.is1ins))
-    locs = torch.cat(locs, 0)
-    superpoint = torch.cat(sps, 0).long()
+    out = assemble_batch([_tuple_record(data) for data in batch], shift_sp_instances=False,
+                         full_scale_min=full_scale_min)
+    # (a host dict may still be edited: ``harness.to_device`` takes the slots from the labels it uploads)
+    del out["sp_instance_slots"]
+    superpoint = out["superpoint"]
     if len(np.unique(superpoint.numpy())) != int(superpoint.max()) + 1:
         raise ValueError("superpoint ids are not dense after batching (:422)")
-    spatial_shape = np.clip((locs.max(0)[0][1:] + 1).numpy(), full_scale_min, None)
-    voxel_locs, p2v_map, v2p_map = pointgroup_ops.voxelization_idx(locs, len(batch), mode)
-    GIs = [GraphConvInfo(torch.cat(edge_sorted, 0).t().contiguous(), torch.cat(feat_sorted, 0).float(), sp_bias)]
-    edges = torch.cat(edges_ext, 0)
-    return {
-        "locs": locs, "locs_offset": torch.stack(loc_offsets), "voxel_locs": voxel_locs, "p2v_map": p2v_map,
-        "v2p_map": v2p_map, "locs_float": torch.cat(locs_float, 0).to(torch.float32),
-        "feats": torch.cat(feats, 0).to(torch.float32), "semantic_labels": torch.cat(sems, 0).long(),
-        "instance_labels": torch.cat(inss, 0).long(), "instance_info": torch.cat(infos, 0).to(torch.float32),
-        "instance_pointnum": torch.tensor(pointnum, dtype=torch.int),
-        "offsets": torch.tensor(batch_offsets, dtype=torch.int), "spatial_shape": spatial_shape,
-        "superpoint": superpoint, "GIs": GIs, "sp_batch_offsets": torch.tensor(sp_batch_offsets, dtype=torch.int),
-        "edge_u_list": edges[:, 0].contiguous().long(), "edge_v_list": edges[:, 1].contiguous().long(),
-        "edge_src_rows": (int(edges[:, 0].max()) + 1) if edges.shape[0] else 0,   # rows of scatter(.., edge_u)
-        "level_counts": _level_counts(voxel_locs, spatial_shape),      # active voxels of the strided UNet levels
-        "is1ins_labels": torch.cat(is1ins, 0),
-        "superpoint_semantic_labels": torch.cat(sp_sem, 0).long(),
-        "superpoint_instance_labels": torch.cat(sp_ins, 0).long(),
-        "superpoint_offset_vector": torch.cat(sp_off, 0).to(torch.float32),
-        "superpoint_instance_voxel_num": torch.log(torch.cat(sp_vox, 0).to(torch.float32)),
-        "superpoint_instance_size": torch.cat(sp_size, 0).to(torch.float32),
-        "scene_list": scene_list,
-    }
+    return voxelize_and_count(out, len(batch), mode, 5)
 
 
 def synthetic_scene_to_reference_format(sc):
@@ -782,82 +869,30 @@ class DeviceScenePrep(ScenePrep):
         return P
 
 
+def _prepared_record(it):
+    """:class:`PreparedScene` -> record"""
+    vs = it.vs
+    return SceneRecord(
+        name=it.scene, loc=it.loc, loc_float=it.loc_float, feat=it.feat, sem=it.sem, ins=it.ins, sp=it.sp, S=it.S,
+        n_inst=it.inst_num, sp_sem=vs["semantic_label"].long(), sp_ins=vs["instance_label"].long(),
+        sp_off=vs["superpoint_offset_vector"].to(torch.float32), sp_size=vs["instance_size"].to(torch.float32),
+        sp_vox=it.logvox, sp_vox_is_log=True, edges=it.edges, edge_feats=it.f.float(), loc_offset=it.loc_offset,
+        inst_info=it.inst_info, inst_pointnum=it.inst_pointnum, is1ins=it.is1ins,
+        extent=it.extent, edge_src_max=it.edge_src_max, sp_ins_max=it.sp_ins_max)
+
+
 def collate_prepared(items, mode=4, n_levels=5):
     """``collate_fn`` (:343-474) over :class:`PreparedScene` items, on the device: returns what
     ``harness.to_device(collate_fn([...]), device)`` returns, the per-point tensors never leaving the device.  The host
     thread lays the batch out from the items' counts."""
-    import pointgroup_ops
-    import spconv
     import wsis_native as _n
-    from graphnet import GraphConvInfo
-    from harness import FULL_SCALE_MIN, build_batch_graphs
+    from harness import FULL_SCALE_MIN, finish_device_batch
     if not items:
         raise ValueError("empty batch")
     dev = items[0].device
     if torch.device(dev).type != "cuda":
         raise _n.WsisError("collate_prepared runs on the MI355X (there is no CPU fallback)")
-    cols = {k: [] for k in ("locs", "locs_float", "feats", "sem", "ins", "sps", "info", "pointnum", "sp_sem", "sp_ins",
-                            "sp_off", "sp_vox", "sp_size", "edge_sorted", "feat_sorted", "edges_ext", "is1ins")}
-    batch_offsets, sp_batch_offsets, slots = [0], [0], []
-    sp_bias, total_inst, edge_src_rows = 0, 0, 0
-    extent = np.zeros(3, dtype=np.int64)
     with torch.cuda.device(dev):
-        for i, it in enumerate(items):
-            this_bias = sp_bias
-            cols["sps"].append(it.sp + this_bias if this_bias else it.sp)
-            sp_bias = this_bias + it.S
-            sp_batch_offsets.append(sp_bias)
-            cols["ins"].append(torch.where(it.ins != -100, it.ins + total_inst, it.ins) if total_inst else it.ins)
-            total_inst += it.inst_num
-            batch_offsets.append(batch_offsets[-1] + it.n)
-            cols["locs"].append(torch.cat([torch.full((it.n, 1), i, dtype=torch.int64, device=it.loc.device), it.loc], 1))
-            cols["locs_float"].append(it.loc_float)
-            cols["feats"].append(it.feat)
-            cols["sem"].append(it.sem)
-            cols["info"].append(it.inst_info)
-            cols["pointnum"].append(it.inst_pointnum)
-            cols["sp_sem"].append(it.vs["semantic_label"].long())
-            cols["sp_ins"].append(it.vs["instance_label"].long())
-            cols["sp_off"].append(it.vs["superpoint_offset_vector"].to(torch.float32))
-            cols["sp_vox"].append(it.logvox)
-            cols["sp_size"].append(it.vs["instance_size"].to(torch.float32))
-            order = torch.argsort(it.edges[:, 1], stable=True)          # ecc/GraphConvInfo.py:54-70 (sorted by target)
-            Eb = it.edges + this_bias if this_bias else it.edges
-            cols["edge_sorted"].append(Eb[order])
-            cols["feat_sorted"].append(it.f[order])
-            cols["edges_ext"].append(Eb)
-            cols["is1ins"].append(it.is1ins)
-            if it.E:
-                edge_src_rows = max(edge_src_rows, it.edge_src_max + this_bias + 1)
-            slots.append(max(it.sp_ins_max + 1, 1) if it.S else 1)
-            extent = np.maximum(extent, it.extent)
-
-        def cat(k):
-            return (cols[k][0] if len(cols[k]) == 1 else torch.cat(cols[k], 0)).contiguous()
-        locs = cat("locs")
-        edges = cat("edges_ext")
-        out = {
-            "locs": locs, "locs_offset": torch.stack([it.loc_offset for it in items]),
-            "locs_float": cat("locs_float"), "feats": cat("feats"), "semantic_labels": cat("sem"),
-            "instance_labels": cat("ins"), "instance_info": cat("info"), "instance_pointnum": cat("pointnum"),
-            "offsets": torch.tensor(batch_offsets, dtype=torch.int), "spatial_shape": np.clip(extent, FULL_SCALE_MIN, None),
-            "superpoint": cat("sps"),
-            "GIs": [GraphConvInfo(cat("edge_sorted").t().contiguous(), cat("feat_sorted").float(), sp_bias)],
-            "sp_batch_offsets": torch.tensor(sp_batch_offsets, dtype=torch.int),
-            "edge_u_list": edges[:, 0].contiguous(), "edge_v_list": edges[:, 1].contiguous(),
-            "edge_src_rows": edge_src_rows, "is1ins_labels": cat("is1ins"),
-            "superpoint_semantic_labels": cat("sp_sem"), "superpoint_instance_labels": cat("sp_ins"),
-            "superpoint_offset_vector": cat("sp_off"), "superpoint_instance_voxel_num": cat("sp_vox"),
-            "superpoint_instance_size": cat("sp_size"), "scene_list": [it.scene for it in items],
-            "sp_instance_slots": slots,
-        }
-        voxel_locs, p2v_map, v2p_map = pointgroup_ops.voxelization_idx(locs, len(items), mode)
-        counts = spconv.ops.level_voxel_counts_device(voxel_locs, out["spatial_shape"], n_levels)
-        out.update(voxel_locs=voxel_locs, p2v_map=p2v_map, v2p_map=v2p_map)
-        out["level_counts"] = [int(c) for c in counts.tolist()]
-        out["voxel_coords_int"] = voxel_locs.int().contiguous()
-        ev = torch.cuda.Event()
-        ev.record()
-        out["coords_ready_event"] = ev
-        build_batch_graphs(out)
-    return out
+        out = assemble_batch([_prepared_record(it) for it in items], shift_sp_instances=False,
+                             full_scale_min=FULL_SCALE_MIN)
+        return finish_device_batch(voxelize_and_count(out, len(items), mode, n_levels))

@@ -57,6 +57,33 @@ def test_packed_collate_equals_host_collate(seeds, room):
         assert torch.equal(dev[k].perm, host[k].perm) and torch.equal(dev[k].offsets, host[k].offsets), k
 
 
+def test_a_scene_without_edges_inside_the_batch():
+    """three small scenes, the middle one with an empty edge list: both device-side collates still equal
+    ``to_device(collate(scenes))`` (the superpoint offsets behind it, ``edge_src_rows`` from the packs' numbers)"""
+    scenes = [harness.make_scene(s, room=(1.0, 0.9, 0.8), n_box=2) for s in (5, 6, 7)]
+    scenes[1] = dict(scenes[1], edges=np.zeros((0, 2), dtype=np.int64), edge_feats=np.zeros((0, 13), dtype=np.float32))
+    host = harness.to_device(harness.collate(scenes), DEV)
+    for dev in (harness.collate_packed([harness.pack_scene(sc) for sc in scenes], DEV),
+                harness.collate_device(scenes, DEV)):
+        torch.cuda.synchronize()
+        for k in ("voxel_locs", "p2v_map", "v2p_map", "voxel_coords_int", "locs_float", "feats", "superpoint",
+                  "edge_u_list", "edge_v_list", "semantic_labels", "instance_labels", "superpoint_semantic_labels",
+                  "superpoint_instance_labels", "superpoint_offset_vector", "superpoint_instance_voxel_num",
+                  "superpoint_instance_size"):
+            assert dev[k].is_cuda and dev[k].dtype == host[k].dtype, k
+            assert torch.equal(dev[k], host[k]), k
+        for k in ("offsets", "sp_batch_offsets"):
+            assert torch.equal(dev[k].cpu(), host[k].cpu()), k
+        assert list(dev["level_counts"]) == list(host["level_counts"])
+        assert np.array_equal(dev["spatial_shape"], host["spatial_shape"])
+        assert dev["sp_instance_slots"] == host["sp_instance_slots"] and dev["edge_src_rows"] == host["edge_src_rows"]
+        gd, gh = dev["GIs"][0], host["GIs"][0]
+        assert gd.num_nodes == gh.num_nodes and torch.equal(gd.get_pyg_buffers(), gh.get_pyg_buffers())
+        assert torch.equal(gd.get_buffers(), gh.get_buffers())
+        for k in ("superpoint_csr", "p2v_csr"):
+            assert torch.equal(dev[k].perm, host[k].perm) and torch.equal(dev[k].offsets, host[k].offsets), k
+
+
 def test_a_step_on_the_packed_batch_gives_the_same_loss():
     cfg = harness.default_cfg()
     scenes = [harness.bench_scene(8, room=(2.0, 1.6, 1.2), n_box=2)]
