@@ -176,6 +176,14 @@ _HIP_SIGS = {
     "wsis_gp_label_mode": (I32, [P, P, P, I64, I64, P, P, P]),
     "wsis_gp_neighbors": (I32, [P, I64, I32, F64, P, P, P, P]),
     "wsis_gp_edge_features": (I32, [P, P, P, I64, I64, P, I64, P, P, P, P, P, P, P, P]),
+    "wsis_pt_bins_workspace_bytes": (I64, [I64]),
+    "wsis_pt_bins": (I32, [P, I64, F32, P, P, P, P, I64, P]),
+    "wsis_pt_prune_accumulate": (I32, [P, P, P, I32, P, P, I64, I64, P, P, P, P, P]),
+    "wsis_pt_knn_workspace_bytes": (I64, [I64]),
+    "wsis_pt_knn": (I32, [P, I64, I32, F64, P, P, P, P, I64, P]),
+    "wsis_pt_geof": (I32, [P, P, I64, I32, P, P, P, P]),
+    "wsis_pt_edge_features_workspace_bytes": (I64, [I64, I32]),
+    "wsis_pt_edge_features": (I32, [P, P, P, P, I64, I32, I32, F32, P, P, P, P, P, P, P, I64, P]),
     "wsis_mask_overlap_chunk": (I32, []),
     "wsis_mask_overlap_tile_rows": (I32, [I32]),
     "wsis_mask_overlap_workspace_bytes": (I64, [I64, I64, I32]),

@@ -862,6 +862,59 @@ int wsis_gp_edge_features(const float* d_xyz, const int32_t* d_perm, const int32
                           const float* d_centroid, const float* d_length, const float* d_surface, const float* d_volume,
                           float* d_out, void* stream);
 
+/* ---- the S3DIS partition front end: the array stages of generate_SPG_superpoint (data/S3DIS/partition/
+ * partition_S3DIS.py:81-115) before the l0 cut-pursuit solver, which stays the caller's (csrc/partition.hip; driven by
+ * wsis_partition).  No floating-point atomics, fixed summation order, uncontracted products: two calls give the same
+ * bytes.  Every index read from a table is clamped to its table before use.
+ *
+ * wsis_pt_bins: the voxel of every point, libply_c.prune ply_c/ply_c.cpp:311-337.  d_min3 fp32 [3] = the per-axis
+ * minimum of d_xyz fp32 [N,3]; d_coords int64 [N,4] = (0, bx, by, bz), b = floorf((x - x_min) / voxel) with an fp32
+ * subtraction and a correctly rounded fp32 division, NOT clamped to n_bin (the reference does not: a point at x_max on
+ * a cell boundary has bin n_bin) -- the rows wsis_voxelize_idx_map takes, whose first-occurrence ids are the insertion
+ * index of the reference's std::map (:175-189).  *d_nonfinite = 1 if a coordinate is NaN or infinite (the bins of such
+ * input are defined but meaningless: the caller refuses it), else 0.  d_ws: wsis_pt_bins_workspace_bytes(N). */
+int64_t wsis_pt_bins_workspace_bytes(int64_t N);
+int wsis_pt_bins(const float* d_xyz, int64_t N, float voxel, int64_t* d_coords, float* d_min3, int32_t* d_nonfinite,
+                 void* d_ws, int64_t ws_bytes, void* stream);
+/* The voxel averages of libply_c.prune (ply_c.cpp:255-290, 368-390) over the point CSR d_perm / d_offsets of
+ * wsis_segment_csr(point_to_voxel) (a row lists its points in ascending index order): one sequential chain per voxel.
+ * d_out_xyz fp32 [V,3] = the fp32 sum of the coordinates in point order, divided by (float)count; d_out_rgb uint8 [V,3]
+ * = (uint8)((float)sum / (float)count) of the uint32 colour sums (truncation); d_count int32 [V]; with d_labels int32 [N]
+ * (else NULL) d_label_hist uint32 [V, n_labels + 1], the label being the column.  A label outside [0, n_labels] is not
+ * counted: the caller refuses such input before the launch (the reference's .at() throws). */
+int wsis_pt_prune_accumulate(const float* d_xyz, const uint8_t* d_rgb, const int32_t* d_labels, int32_t n_labels,
+                             const int32_t* d_perm, const int32_t* d_offsets, int64_t N, int64_t V, float* d_out_xyz,
+                             uint8_t* d_out_rgb, uint32_t* d_label_hist, int32_t* d_count, void* stream);
+/* NearestNeighbors(k + 1, 'kd_tree').kneighbors of graphs.py:34-38: the exact k nearest neighbours of every point among
+ * the same V points.  d2 = (dx*dx + dy*dy) + dz*dz on coordinates widened to fp64; row v of d_nbr int32 [V,k] / d_dist2
+ * fp64 [V,k] ascends in (d2, id), self excluded by id.  1 <= k <= 64, V >= k + 1.  The points are sorted by the key of a
+ * uniform grid cell (edge `cell`; cell <= 0: chosen from the bounding box and V) and cells are found through the sorted
+ * keys: the workspace is O(V) whatever the extent.  One wave per query visits the cells ring by ring and stops when the
+ * k-th d2 is below the squared distance to the nearest face of the searched block; after 3 rings it scans every point
+ * instead.  d_stats int32 [V,2] (may be NULL): candidates evaluated, 1 if the query took that scan. */
+int64_t wsis_pt_knn_workspace_bytes(int64_t V);
+int wsis_pt_knn(const float* d_xyz, int64_t V, int32_t k, double cell, int32_t* d_nbr, double* d_dist2, int32_t* d_stats,
+                void* d_ws, int64_t ws_bytes, void* stream);
+/* libply_c.compute_geof (ply_c.cpp:406-463) in fp64: per point the mean and the six central second moments of the k + 1
+ * positions (self, then d_nbr[v][0..k)), divided by k + 1; eigenvalues and eigenvectors by cyclic Jacobi (at most 12
+ * sweeps), eigenvalues descending and clamped at 0; d_geof fp32 [V,4] = linearity, planarity, scattering, verticality of
+ * :448-458, each rounded to fp32 once (lambda_0 = 0 gives NaN, as the reference's expressions do).  d_cov6 fp64 [V,6] =
+ * (xx, yy, zz, xy, xz, yz) and d_ev3 fp64 [V,3] may be NULL. */
+int wsis_pt_geof(const float* d_xyz, const int32_t* d_nbr, int64_t V, int32_t k, float* d_geof, double* d_cov6,
+                 double* d_ev3, void* stream);
+/* partition_S3DIS.py:105-108 and the graph arrays of graphs.py:69-74.  d_features fp32 [V,7] = linearity, planarity,
+ * scattering, 2 * verticality, (float)((double)c / 255.0) of the three colours; d_source / d_target uint32 [V * k_adj] =
+ * v repeated, the first k_adj neighbours of v; d_distances fp32 = (float)sqrt(dist2); *d_mean fp32 = the fp64 sum of
+ * those distances in index order over their count -- two levels of sequential chains: every chunk of 256 consecutive
+ * distances is added in index order, then the chunk sums are added in index order (the result depends on that chunk
+ * length alone) --,
+ * rounded once; d_edge_weight = 1.f / (lambda + d / mean) in fp32.  1 <= k_adj <= k <= 64. */
+int64_t wsis_pt_edge_features_workspace_bytes(int64_t V, int32_t k_adj);
+int wsis_pt_edge_features(const float* d_geof, const uint8_t* d_rgb, const int32_t* d_nbr, const double* d_dist2, int64_t V,
+                          int32_t k, int32_t k_adj, float lambda, float* d_features, uint32_t* d_source,
+                          uint32_t* d_target, float* d_distances, float* d_edge_weight, float* d_mean, void* d_ws,
+                          int64_t ws_bytes, void* stream);
+
 /* ---- evaluation counts: what evaluation/basic/ins_seg_evaluator.py:70-115 (assign_instances_for_scan),
  * evaluation/basic/instances.py:53-85 (VertInstance.get_instances), utils/eval_s3dis.py:42-112 and
  * evaluation/basic/sem_seg_evaluator.py:34-37 (fill_confusion) count per scene, called from test_scannetv2.py:133-143,
