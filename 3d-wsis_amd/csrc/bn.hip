@@ -10,7 +10,9 @@
 // defined ONCE (bn_fwd_elem, bn_bwd_elem, bn_bwd_dx, bn_shifted_mean_var, common.h bn_centred_mean_var / bn_store_stats,
 // bn_chunk_walk / bn_lane_fold / bn_ticket_sum); every launch form -- stand-alone two-launch and one-launch, two-level
 // from centred partials, small finish + apply, polled finish + apply (EXPERIMENTAL) -- is a walk around those, so the
-// forms agree bit for bit by construction.
+// forms agree bit for bit by construction.  The stand-alone reductions and the backward apply are templates on the element
+// type: the 16-bit entry points (wsis_bn_stats_lp, wsis_bn_bwd_lp, wsis_bn_apply_lp) are the fp32 kernels reading bf16 /
+// fp16 rows widened exactly, with the fp32 forms' launch plans (bn_stats_run, bn_bwd_reduce_run).
 #include <cstdlib>
 #include <initializer_list>
 
@@ -33,13 +35,42 @@ constexpr int BN_THREADS = 256;
 struct f4 {
   float v[4];
 };
-__device__ __forceinline__ f4 ld4(const float* p, bool vec) {
+// four consecutive elements of an fp32 / bf16 / fp16 tensor as fp32 (16-bit values widen exactly), and back: float4 moves
+// 16 bytes, a 16-bit quad 8 bytes (one ushort4); 16-bit stores round to nearest even
+template <typename T>
+__device__ __forceinline__ float4 bn_ld4(const T* p, int64_t t) {
+  if constexpr (sizeof(T) == 4) {
+    return reinterpret_cast<const float4*>(p)[t];
+  } else {
+    const ushort4 u = reinterpret_cast<const ushort4*>(p)[t];
+    return make_float4((float)__builtin_bit_cast(T, u.x), (float)__builtin_bit_cast(T, u.y),
+                       (float)__builtin_bit_cast(T, u.z), (float)__builtin_bit_cast(T, u.w));
+  }
+}
+template <typename T>
+__device__ __forceinline__ void bn_st4(T* p, int64_t t, float4 v) {
+  if constexpr (sizeof(T) == 4) {
+    reinterpret_cast<float4*>(p)[t] = v;
+  } else {
+    ushort4 u;
+    u.x = __builtin_bit_cast(unsigned short, (T)v.x);
+    u.y = __builtin_bit_cast(unsigned short, (T)v.y);
+    u.z = __builtin_bit_cast(unsigned short, (T)v.z);
+    u.w = __builtin_bit_cast(unsigned short, (T)v.w);
+    reinterpret_cast<ushort4*>(p)[t] = u;
+  }
+}
+
+// four channels of a row as fp32 (T = float, __bf16 or _Float16): one bn_ld4 quad where the row allows it.  The reductions
+// and the backward apply below are written once for the three element types.
+template <typename T>
+__device__ __forceinline__ f4 ld4(const T* p, bool vec) {
   f4 r;
   if (vec) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
+    const float4 t = bn_ld4(p, 0);
     r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
   } else {
-    r.v[0] = p[0]; r.v[1] = p[1]; r.v[2] = p[2]; r.v[3] = p[3];
+    r.v[0] = (float)p[0]; r.v[1] = (float)p[1]; r.v[2] = (float)p[2]; r.v[3] = (float)p[3];
   }
   return r;
 }
@@ -96,10 +127,11 @@ __device__ __forceinline__ float bn_bwd_dx(BnDz z, const BnBwdCoef& k, int e, fl
 // sigma: 10 % off); a pivot within sigma / sqrt(8) of the mean keeps sum (x - K)^2 within 12 % of the centred sum (a
 // one-row pivot doubles it, and with it the rounding error: median gradient error against the fp64 oracle 3.7e-4 ->
 // 6.6e-4)
-__device__ __forceinline__ float bn_pivot(const float* __restrict__ x, int64_t M, int C, int c) {
+template <typename T>
+__device__ __forceinline__ float bn_pivot(const T* __restrict__ x, int64_t M, int C, int c) {
   const int n = M < 8 ? (int)M : 8;
   float s = 0.0f;
-  for (int r = 0; r < n; ++r) s += x[(int64_t)r * C + c];
+  for (int r = 0; r < n; ++r) s += (float)x[(int64_t)r * C + c];
   return s / (float)n;
 }
 
@@ -114,9 +146,11 @@ __device__ __forceinline__ BnMeanVar bn_shifted_mean_var(double S, double Q, flo
 }
 
 // What row r contributes to the two fp32 sums (sa, sb) of a thread that owns channels c .. c + 3: init() loads the
-// per-channel values once, row() adds one row.
+// per-channel values once, row() adds one row.  T: element type of x (and dy): float, or __bf16 / _Float16 widened as
+// they are read -- the sums of a 16-bit tensor are the sums of the widened tensor, addition for addition.
+template <typename T>
 struct BnStatsAcc {      // forward: (sum, sum of squares) of x - K
-  const float* __restrict__ x;
+  const T* __restrict__ x;
   float K[4];
   __device__ __forceinline__ void init(int64_t M, int C, int c) {
 #pragma unroll
@@ -130,7 +164,7 @@ struct BnStatsAcc {      // forward: (sum, sum of squares) of x - K
       for (int e = 0; e < 4; ++e) v[e] = t.v[e] - K[e];
     } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (c + e < C) ? x[r * C + c + e] - K[e] : 0.0f;
+      for (int e = 0; e < 4; ++e) v[e] = (c + e < C) ? (float)x[r * C + c + e] - K[e] : 0.0f;
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -139,9 +173,10 @@ struct BnStatsAcc {      // forward: (sum, sum of squares) of x - K
     }
   }
 };
+template <typename T>
 struct BnBwdAcc {        // backward: (sum dz, sum dz * xhat)
-  const float* __restrict__ x;
-  const float* __restrict__ dy;
+  const T* __restrict__ x;
+  const T* __restrict__ dy;
   const float* __restrict__ mean;
   const float* __restrict__ var;
   const float* __restrict__ gamma;
@@ -166,8 +201,8 @@ struct BnBwdAcc {        // backward: (sum dz, sum dz * xhat)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const bool ok = c + e < C;
-        xv[e] = ok ? x[r * C + c + e] : 0.0f;
-        dv[e] = ok ? dy[r * C + c + e] : 0.0f;
+        xv[e] = ok ? (float)x[r * C + c + e] : 0.0f;
+        dv[e] = ok ? (float)dy[r * C + c + e] : 0.0f;
       }
     }
 #pragma unroll
@@ -228,21 +263,23 @@ __device__ __forceinline__ void bn_partial_body(Acc acc, int64_t M, int C, int C
 }
 
 // forward: partial sums of x - K and (x - K)^2
-__global__ __launch_bounds__(BN_THREADS) void bn_stats_partial_kernel(const float* __restrict__ x, int64_t M, int C,
-                                                                      int Cp, float* __restrict__ partial) {
+template <typename T>
+__global__ __launch_bounds__(BN_THREADS) void bn_stats_partial_kernel(const T* __restrict__ x, int64_t M, int C, int Cp,
+                                                                      float* __restrict__ partial) {
   __shared__ float s_a[BN_THREADS * 4];
   __shared__ float s_b[BN_THREADS * 4];
-  bn_partial_body(BnStatsAcc{x}, M, C, Cp, partial, s_a, s_b);
+  bn_partial_body(BnStatsAcc<T>{x}, M, C, Cp, partial, s_a, s_b);
 }
 
 // backward pass 1: per-workgroup partial (sum dz, sum dz*xhat) per channel
+template <typename T>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_partial_kernel(
-    const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
+    const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
     int relu, int64_t M, int C, int Cp, float* __restrict__ partial) {
   __shared__ float s_a[BN_THREADS * 4];
   __shared__ float s_b[BN_THREADS * 4];
-  bn_partial_body(BnBwdAcc{x, dy, mean, var, gamma, beta, eps, relu}, M, C, Cp, partial, s_a, s_b);
+  bn_partial_body(BnBwdAcc<T>{x, dy, mean, var, gamma, beta, eps, relu}, M, C, Cp, partial, s_a, s_b);
 }
 
 // pass 2: one wavefront per channel: lanes stride over the partials (fp64), fixed butterfly => deterministic.
@@ -263,8 +300,9 @@ __device__ __forceinline__ void bn_final_sums(const float* __restrict__ partial,
   B = wave_sum_f64(b);
 }
 
+template <typename T>
 __global__ __launch_bounds__(64) void bn_stats_final_kernel(const float* __restrict__ partial, int nblk, int C,
-                                                            int Cp, int64_t M, const float* __restrict__ x0,
+                                                            int Cp, int64_t M, const T* __restrict__ x0,
                                                             float* __restrict__ mean,
                                                             float* __restrict__ var,
                                                             float* __restrict__ running_mean,
@@ -351,13 +389,14 @@ __device__ __forceinline__ void bn_small_body(Acc& acc, int64_t M, int C, int c0
   block_sum2_f64(a, b, sh);
 }
 
-__global__ __launch_bounds__(BN_SMALL_THREADS) void bn_stats_small_kernel(const float* __restrict__ x, int64_t M, int C,
+template <typename T>
+__global__ __launch_bounds__(BN_SMALL_THREADS) void bn_stats_small_kernel(const T* __restrict__ x, int64_t M, int C,
                                                                     float* __restrict__ mean, float* __restrict__ var,
                                                                     float* __restrict__ running_mean,
                                                                     float* __restrict__ running_var, float momentum) {
   __shared__ double sh[BN_SMALL_THREADS / 64 * 8];
   const int c0 = blockIdx.x * 4;
-  BnStatsAcc acc{x};
+  BnStatsAcc<T> acc{x};
   double a[4], b[4];
   bn_small_body(acc, M, C, c0, sh, a, b);
   const float K[4] = {acc.K[0], acc.K[1], acc.K[2], acc.K[3]};      // (indexed by the thread: an array of its own)
@@ -367,13 +406,14 @@ __global__ __launch_bounds__(BN_SMALL_THREADS) void bn_stats_small_kernel(const 
   }
 }
 
+template <typename T>
 __global__ __launch_bounds__(BN_SMALL_THREADS) void bn_bwd_small_kernel(
-    const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
+    const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
     int relu, int64_t M, int C, float* __restrict__ dgamma, float* __restrict__ dbeta) {
   __shared__ double sh[BN_SMALL_THREADS / 64 * 8];
   const int c0 = blockIdx.x * 4;
-  BnBwdAcc acc{x, dy, mean, var, gamma, beta, eps, relu};
+  BnBwdAcc<T> acc{x, dy, mean, var, gamma, beta, eps, relu};
   double a[4], b[4];
   bn_small_body(acc, M, C, c0, sh, a, b);
   if (threadIdx.x < 4 && c0 + (int)threadIdx.x < C) {
@@ -575,32 +615,6 @@ __device__ __forceinline__ float bn_ld_stat(const float* p) {
   return *p;
 }
 
-// four consecutive elements of an fp32 / bf16 / fp16 tensor as fp32 (16-bit values widen exactly), and back: float4 moves
-// 16 bytes, a 16-bit quad 8 bytes (one ushort4); 16-bit stores round to nearest even
-template <typename T>
-__device__ __forceinline__ float4 bn_ld4(const T* p, int64_t t) {
-  if constexpr (sizeof(T) == 4) {
-    return reinterpret_cast<const float4*>(p)[t];
-  } else {
-    const ushort4 u = reinterpret_cast<const ushort4*>(p)[t];
-    return make_float4((float)__builtin_bit_cast(T, u.x), (float)__builtin_bit_cast(T, u.y),
-                       (float)__builtin_bit_cast(T, u.z), (float)__builtin_bit_cast(T, u.w));
-  }
-}
-template <typename T>
-__device__ __forceinline__ void bn_st4(T* p, int64_t t, float4 v) {
-  if constexpr (sizeof(T) == 4) {
-    reinterpret_cast<float4*>(p)[t] = v;
-  } else {
-    ushort4 u;
-    u.x = __builtin_bit_cast(unsigned short, (T)v.x);
-    u.y = __builtin_bit_cast(unsigned short, (T)v.y);
-    u.z = __builtin_bit_cast(unsigned short, (T)v.z);
-    u.w = __builtin_bit_cast(unsigned short, (T)v.w);
-    reinterpret_cast<ushort4*>(p)[t] = u;
-  }
-}
-
 // TI / TO: element types of x and y (float, __bf16 or _Float16).  The arithmetic is fp32 whatever they are: a 16-bit x is
 // widened exactly, y is rounded once at the store -- the 16-bit forms equal the fp32 form on the widened x, rounded.
 template <bool COHERENT, typename TI = float, typename TO = float>
@@ -685,14 +699,15 @@ void launch_bn_apply_lp(const void* x, const float* mean, const float* var, cons
                        gamma, beta, eps, relu, static_cast<TI*>(y), M, C);
 }
 
-// backward pass 2 (bn_bwd_dx)
-template <bool COHERENT>     // COHERENT: dgamma / dbeta come from other workgroups of this launch (see bn_ld_stat)
-__device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ x, const float* __restrict__ dy,
+// backward pass 2 (bn_bwd_dx).  T: element type of x, dy and the addend, TO: of dx (T, or float for the unrounded dx of a
+// 16-bit pass).  The arithmetic is fp32 whatever they are; a 16-bit dx is rounded once at the store, addend included.
+template <bool COHERENT, typename T, typename TO>     // COHERENT: dgamma / dbeta come from other workgroups of this launch (see bn_ld_stat)
+__device__ __forceinline__ void bn_bwd_apply_body(const T* __restrict__ x, const T* __restrict__ dy,
                                                   const float* __restrict__ mean, const float* __restrict__ var,
                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
                                                   const float* dgamma, const float* dbeta,
-                                                  const float* __restrict__ addend, float eps, int relu, int training,
-                                                  float* __restrict__ dx, int64_t M, int C) {
+                                                  const T* __restrict__ addend, float eps, int relu, int training,
+                                                  TO* __restrict__ dx, int64_t M, int C) {
   const int64_t total = M * C;
   const float inv_m = 1.0f / (float)M;
   const bool vec = (C & 3) == 0;
@@ -740,8 +755,8 @@ __device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ x, c
       float o0[4], o1[4];
       one(tx0.v, td0.v, ta0.v, o0);
       one(tx1.v, td1.v, ta1.v, o1);
-      reinterpret_cast<float4*>(dx)[t] = make_float4(o0[0], o0[1], o0[2], o0[3]);
-      reinterpret_cast<float4*>(dx)[u] = make_float4(o1[0], o1[1], o1[2], o1[3]);
+      bn_st4(dx, t, make_float4(o0[0], o0[1], o0[2], o0[3]));
+      bn_st4(dx, u, make_float4(o1[0], o1[1], o1[2], o1[3]));
     }
   }
   for (; t < totalw; t += stride) {
@@ -760,24 +775,25 @@ __device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ x, c
         for (int e = 0; e < 4; ++e) av[e] = ta.v[e];
       }
     } else {
-      xv[0] = x[t];
-      dv[0] = dy[t];
-      if (addend) av[0] = addend[t];
+      xv[0] = (float)x[t];
+      dv[0] = (float)dy[t];
+      if (addend) av[0] = (float)addend[t];
     }
     one(xv, dv, av, ov);
     if (vec)
-      reinterpret_cast<float4*>(dx)[t] = make_float4(ov[0], ov[1], ov[2], ov[3]);
+      bn_st4(dx, t, make_float4(ov[0], ov[1], ov[2], ov[3]));
     else
-      dx[t] = ov[0];
+      dx[t] = (TO)ov[0];
   }
 }
 
-__global__ void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+template <typename T, typename TO>
+__global__ void bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                     const float* __restrict__ mean, const float* __restrict__ var,
                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                     const float* __restrict__ dgamma, const float* __restrict__ dbeta,
-                                    const float* __restrict__ addend, float eps, int relu, int training,
-                                    float* __restrict__ dx, int64_t M, int C) {
+                                    const T* __restrict__ addend, float eps, int relu, int training,
+                                    TO* __restrict__ dx, int64_t M, int C) {
   bn_bwd_apply_body<false>(x, dy, mean, var, gamma, beta, dgamma, dbeta, addend, eps, relu, training, dx, M, C);
 }
 
@@ -1072,14 +1088,75 @@ static int bn_apply_grid(int64_t M, int C) {
   return (int)g;
 }
 
-static int launch_bn_bwd_apply(const float* d_x, const float* d_dy, const float* d_mean, const float* d_var,
+template <typename T, typename TO>
+static int launch_bn_bwd_apply(const T* d_x, const T* d_dy, const float* d_mean, const float* d_var,
                                const float* d_gamma, const float* d_beta, const float* d_dgamma, const float* d_dbeta,
-                               const float* d_addend, float eps, int relu, int training, float* d_dx, int64_t M, int C,
+                               const T* d_addend, float eps, int relu, int training, TO* d_dx, int64_t M, int C,
                                hipStream_t st) {
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(bn_apply_grid(M, C)), dim3(256), 0, st, d_x, d_dy, d_mean, d_var, d_gamma,
-                     d_beta, d_dgamma, d_dbeta, d_addend, eps, relu, training, d_dx, M, C);
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, TO>), dim3(bn_apply_grid(M, C)), dim3(256), 0, st, d_x, d_dy, d_mean, d_var,
+                     d_gamma, d_beta, d_dgamma, d_dbeta, d_addend, eps, relu, training, d_dx, M, C);
   WSIS_LAUNCH_CHECK();
   return WSIS_OK;
+}
+
+// The launch plan of the stand-alone statistics (wsis_bn_stats, wsis_bn_stats_lp) and of the stand-alone backward
+// reduction (wsis_bn_bwd, wsis_bn_bwd_lp): one launch up to bn_small_rows() rows, partial + final above.  The element
+// type changes the loads only: grids, trees and the branch by M are the same for fp32 and 16-bit tensors.
+template <typename T>
+static int bn_stats_run(const T* d_x, int64_t M, int C, float* d_mean, float* d_var, float* d_running_mean,
+                        float* d_running_var, float momentum, void* d_ws, hipStream_t st) {
+  const int Cp = (C + 3) / 4 * 4;
+  const int nblk = bn_nblk(M, Cp);
+  float* partial = static_cast<float*>(d_ws);
+  WSIS_REQUIRE(Cp / 4 <= BN_THREADS, "C > 1024 is not supported");
+  if (M <= bn_small_rows()) {
+    hipLaunchKernelGGL(bn_stats_small_kernel<T>, dim3(Cp / 4), dim3(BN_SMALL_THREADS), 0, st, d_x, M, C, d_mean, d_var,
+                       d_running_mean, d_running_var, momentum);
+    WSIS_LAUNCH_CHECK();
+    return WSIS_OK;
+  }
+  hipLaunchKernelGGL(bn_stats_partial_kernel<T>, dim3(nblk), dim3(BN_THREADS), 0, st, d_x, M, C, Cp, partial);
+  WSIS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bn_stats_final_kernel<T>, dim3(C), dim3(64), 0, st, partial, nblk, C, Cp, M, d_x, d_mean, d_var,
+                     d_running_mean, d_running_var, momentum);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+template <typename T>
+static int bn_bwd_reduce_run(const T* d_x, const T* d_dy, const float* d_mean, const float* d_var, const float* d_gamma,
+                             const float* d_beta, float eps, int relu, float* d_dgamma, float* d_dbeta, int64_t M, int C,
+                             void* d_ws, hipStream_t st) {
+  const int Cp = (C + 3) / 4 * 4;
+  const int nblk = bn_nblk(M, Cp);
+  float* partial = static_cast<float*>(d_ws);
+  WSIS_REQUIRE(Cp / 4 <= BN_THREADS, "C > 1024 is not supported");
+  if (M <= bn_small_rows()) {
+    hipLaunchKernelGGL(bn_bwd_small_kernel<T>, dim3(Cp / 4), dim3(BN_SMALL_THREADS), 0, st, d_x, d_dy, d_mean, d_var,
+                       d_gamma, d_beta, eps, relu, M, C, d_dgamma, d_dbeta);
+    WSIS_LAUNCH_CHECK();
+  } else {
+    hipLaunchKernelGGL(bn_bwd_partial_kernel<T>, dim3(nblk), dim3(BN_THREADS), 0, st, d_x, d_dy, d_mean, d_var, d_gamma,
+                       d_beta, eps, relu, M, C, Cp, partial);
+    WSIS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(64), 0, st, partial, nblk, C, Cp, d_dgamma, d_dbeta);
+    WSIS_LAUNCH_CHECK();
+  }
+  return WSIS_OK;
+}
+// reduction, then dx (d_dx == nullptr: none) as TO = T, or as float when out_fp32
+template <typename T>
+static int bn_bwd_lp_run(const void* d_x, const void* d_dy, const float* d_mean, const float* d_var, const float* d_gamma,
+                         const float* d_beta, float eps, int relu, int training, void* d_dx, int out_fp32,
+                         float* d_dgamma, float* d_dbeta, const void* d_addend, int64_t M, int C, void* d_ws,
+                         hipStream_t st) {
+  const T *x = static_cast<const T*>(d_x), *dy = static_cast<const T*>(d_dy), *ad = static_cast<const T*>(d_addend);
+  const int rc = bn_bwd_reduce_run(x, dy, d_mean, d_var, d_gamma, d_beta, eps, relu, d_dgamma, d_dbeta, M, C, d_ws, st);
+  if (rc != WSIS_OK || !d_dx) return rc;
+  if (out_fp32)
+    return launch_bn_bwd_apply(x, dy, d_mean, d_var, d_gamma, d_beta, d_dgamma, d_dbeta, ad, eps, relu, training,
+                               static_cast<float*>(d_dx), M, C, st);
+  return launch_bn_bwd_apply(x, dy, d_mean, d_var, d_gamma, d_beta, d_dgamma, d_dbeta, ad, eps, relu, training,
+                             static_cast<T*>(d_dx), M, C, st);
 }
 
 // ticket row of a two-level reduction: the caller's sync slot (nullptr without one, or with WSIS_BN_TICKET=0: the finish
@@ -1139,23 +1216,26 @@ int wsis_bn_stats(const float* d_x, int64_t M, int32_t C, float* d_mean, float* 
   WSIS_REQUIRE(M >= 1 && C >= 1 && d_x && d_mean && d_var && d_ws, "bad args");
   WSIS_REQUIRE(ws_bytes >= wsis_bn_workspace_bytes(M, C), "workspace too small");
   WSIS_REQUIRE((d_running_mean == nullptr) == (d_running_var == nullptr), "running stats come in pairs");
-  const int Cp = (C + 3) / 4 * 4;
-  const int nblk = bn_nblk(M, Cp);
-  float* partial = static_cast<float*>(d_ws);
+  return bn_stats_run(d_x, M, C, d_mean, d_var, d_running_mean, d_running_var, momentum, d_ws, as_stream(stream));
+}
+
+// the 16-bit tensors of a pass: rows of C % 8 == 0 elements (16 bytes and multiples), 16-byte aligned bases
+static bool bn_lp_domain(int C, int dtype, std::initializer_list<const void*> ps) {
+  return (dtype == 0 || dtype == 1) && C % 8 == 0 && C <= 1024 && bn_aligned16(ps);
+}
+
+int wsis_bn_stats_lp(const void* d_x, int64_t M, int32_t C, float* d_mean, float* d_var, float* d_running_mean,
+                     float* d_running_var, float momentum, void* d_ws, int64_t ws_bytes, int32_t dtype, void* stream) {
+  WSIS_REQUIRE(M >= 1 && C >= 1 && d_x && d_mean && d_var && d_ws, "bad args");
+  WSIS_REQUIRE(bn_lp_domain(C, dtype, {d_x}), "16-bit BatchNorm: dtype 0 / 1, C % 8 == 0, C <= 1024, 16-byte aligned x");
+  WSIS_REQUIRE(ws_bytes >= wsis_bn_workspace_bytes(M, C), "workspace too small");
+  WSIS_REQUIRE((d_running_mean == nullptr) == (d_running_var == nullptr), "running stats come in pairs");
   hipStream_t st = as_stream(stream);
-  WSIS_REQUIRE(Cp / 4 <= BN_THREADS, "C > 1024 is not supported");
-  if (M <= bn_small_rows()) {
-    hipLaunchKernelGGL(bn_stats_small_kernel, dim3(Cp / 4), dim3(BN_SMALL_THREADS), 0, st, d_x, M, C, d_mean, d_var,
-                       d_running_mean, d_running_var, momentum);
-    WSIS_LAUNCH_CHECK();
-    return WSIS_OK;
-  }
-  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(nblk), dim3(BN_THREADS), 0, st, d_x, M, C, Cp, partial);
-  WSIS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C), dim3(64), 0, st, partial, nblk, C, Cp, M, d_x, d_mean,
-                     d_var, d_running_mean, d_running_var, momentum);
-  WSIS_LAUNCH_CHECK();
-  return WSIS_OK;
+  if (dtype == 0)
+    return bn_stats_run(static_cast<const __bf16*>(d_x), M, C, d_mean, d_var, d_running_mean, d_running_var, momentum,
+                        d_ws, st);
+  return bn_stats_run(static_cast<const _Float16*>(d_x), M, C, d_mean, d_var, d_running_mean, d_running_var, momentum,
+                      d_ws, st);
 }
 
 // ---- column sums of x [M, C] (bias gradient of a Linear layer over M rows): two levels in ONE launch, fixed order.
@@ -1387,25 +1467,27 @@ int wsis_bn_bwd(const float* d_x, const float* d_dy, const float* d_mean, const 
                 int64_t ws_bytes, void* stream) {
   WSIS_REQUIRE(M >= 1 && C >= 1 && d_x && d_dy && d_mean && d_var && d_dgamma && d_dbeta && d_ws, "bad args");
   WSIS_REQUIRE(ws_bytes >= wsis_bn_workspace_bytes(M, C), "workspace too small");
-  const int Cp = (C + 3) / 4 * 4;
-  const int nblk = bn_nblk(M, Cp);
-  float* partial = static_cast<float*>(d_ws);
   hipStream_t st = as_stream(stream);
-  WSIS_REQUIRE(Cp / 4 <= BN_THREADS, "C > 1024 is not supported");
-  if (M <= bn_small_rows()) {
-    hipLaunchKernelGGL(bn_bwd_small_kernel, dim3(Cp / 4), dim3(BN_SMALL_THREADS), 0, st, d_x, d_dy, d_mean, d_var, d_gamma,
-                       d_beta, eps, relu, M, C, d_dgamma, d_dbeta);
-    WSIS_LAUNCH_CHECK();
-  } else {
-    hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(nblk), dim3(BN_THREADS), 0, st, d_x, d_dy, d_mean, d_var, d_gamma,
-                       d_beta, eps, relu, M, C, Cp, partial);
-    WSIS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C), dim3(64), 0, st, partial, nblk, C, Cp, d_dgamma, d_dbeta);
-    WSIS_LAUNCH_CHECK();
-  }
-  if (!d_dx) return WSIS_OK;
+  const int rc = bn_bwd_reduce_run(d_x, d_dy, d_mean, d_var, d_gamma, d_beta, eps, relu, d_dgamma, d_dbeta, M, C, d_ws, st);
+  if (rc != WSIS_OK || !d_dx) return rc;
   return launch_bn_bwd_apply(d_x, d_dy, d_mean, d_var, d_gamma, d_beta, d_dgamma, d_dbeta, d_addend, eps, relu, training,
                              d_dx, M, C, st);
+}
+
+int wsis_bn_bwd_lp(const void* d_x, const void* d_dy, const float* d_mean, const float* d_var, const float* d_gamma,
+                   const float* d_beta, float eps, int32_t relu, int32_t training, void* d_dx, int32_t out_fp32,
+                   float* d_dgamma, float* d_dbeta, const void* d_addend, int64_t M, int32_t C, int32_t dtype, void* d_ws,
+                   int64_t ws_bytes, void* stream) {
+  WSIS_REQUIRE(M >= 1 && C >= 1 && d_x && d_dy && d_mean && d_var && d_dgamma && d_dbeta && d_ws, "bad args");
+  WSIS_REQUIRE(bn_lp_domain(C, dtype, {d_x, d_dy, d_dx, d_addend}),
+               "16-bit BatchNorm: dtype 0 / 1, C % 8 == 0, C <= 1024, 16-byte aligned tensors");
+  WSIS_REQUIRE(ws_bytes >= wsis_bn_workspace_bytes(M, C), "workspace too small");
+  hipStream_t st = as_stream(stream);
+  if (dtype == 0)
+    return bn_bwd_lp_run<__bf16>(d_x, d_dy, d_mean, d_var, d_gamma, d_beta, eps, relu, training, d_dx, out_fp32, d_dgamma,
+                                 d_dbeta, d_addend, M, C, d_ws, st);
+  return bn_bwd_lp_run<_Float16>(d_x, d_dy, d_mean, d_var, d_gamma, d_beta, eps, relu, training, d_dx, out_fp32, d_dgamma,
+                                 d_dbeta, d_addend, M, C, d_ws, st);
 }
 
 int64_t wsis_sync_bytes(void) { return (int64_t)kSyncSlotsTotal * (int64_t)sizeof(SyncSlot); }

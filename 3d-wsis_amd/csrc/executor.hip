@@ -101,15 +101,17 @@ inline bool vec4_ok(const wsis_op& op, const void* p0, const void* p1, const voi
 // by ONE launch up front instead of one small launch per layer.  One workgroup moves a 32x32 tile of one [Cin, Cout]
 // slice through LDS: reads run along Cout, writes along Cin, both coalesced (an element-per-thread version with
 // stride-Cout reads took 103 us for the 49 layers of the UNet, 11 M weights).  The 16-bit passes take the same launch
-// with T = __bf16 / _Float16: every weight rounded to nearest even as it is stored (the values of wsis_weight_cast_lp).
+// with T = __bf16 / _Float16: every weight rounded to nearest even as it is stored (the values of wsis_weight_cast_lp);
+// a `plain` layer is rounded where it stands (transpose = 0: the dIn operand of a 16-bit backward pass).
 constexpr int WT_MAX = 64;
 constexpr int WT_TILE = 32;
 struct WtBatch {
   const float* src[WT_MAX];
-  void* dst[WT_MAX];      // T [K, Cout, Cin]
+  void* dst[WT_MAX];      // T [K, Cout, Cin] ([K, Cin, Cout] when plain)
   int K[WT_MAX], Cin[WT_MAX], Cout[WT_MAX], flip[WT_MAX];
   int start[WT_MAX + 1];   // first tile of each layer
   int n;
+  int plain[WT_MAX];       // 16-bit launches only (behind the fields the fp32 launch reads: that kernel is unchanged)
 };
 
 template <typename T>
@@ -135,6 +137,16 @@ __global__ __launch_bounds__(256) void weight_transpose_batch_kernel(WtBatch b) 
   const float* __restrict__ src = b.src[lo] + (int64_t)ks * Cin * Cout;
   T* __restrict__ dst = static_cast<T*>(b.dst[lo]) + (int64_t)kt * Cin * Cout;
   const int x = threadIdx.x & 31, y0 = threadIdx.x >> 5;
+  if constexpr (sizeof(T) == 2) {
+    if (b.plain[lo]) {      // (uniform over the workgroup)
+#pragma unroll
+      for (int y = y0; y < WT_TILE; y += 8) {
+        const int ci = bi * WT_TILE + y, co = bo * WT_TILE + x;
+        if (ci < Cin && co < Cout) dst[(int64_t)ci * Cout + co] = (T)src[(int64_t)ci * Cout + co];
+      }
+      return;
+    }
+  }
 #pragma unroll
   for (int y = y0; y < WT_TILE; y += 8) {
     const int ci = bi * WT_TILE + y, co = bo * WT_TILE + x;
@@ -210,6 +222,9 @@ struct DwTask {
   int flush_n = 0;
 };
 static int issue_dw_raw(const wsis_op& op, char* dw_ws, int64_t dw_bytes, void* dw_stream) {
+  if (op.flags & WSIS_OPF_LP)        // 16-bit X and dY, fp32 dW (never deferred: the product sums its own slabs)
+    return wsis_spconv_dw_lp(op.in[0], (const int32_t*)op.in[3], (const int32_t*)op.in[4], op.in[2], (float*)op.out[1],
+                             op.M_in, op.M_out, op.K, op.Cin, op.Cout, op.reserved, dw_ws, dw_bytes, dw_stream);
   if (op.flags & WSIS_OPF_BN_IN)     // the forward input was relu(bn(in[0])) applied on the fly: own-rows form
     return wsis_spconv_dw_bn((const float*)op.in[0], (const float*)op.in[7], (const float*)op.in[8], (const float*)op.in[9],
                              (const float*)op.in[10], op.eps, (op.flags & WSIS_OPF_RELU) ? 1 : 0, (const int32_t*)op.in[5],
@@ -371,38 +386,70 @@ inline bool needs_wt(const wsis_op& op, bool on) {
   return false;
 }
 
-// ---- 16-bit ops (WSIS_OPF_LP, evaluation-mode inference): what the executor runs, and why it refuses the rest
+// ---- 16-bit ops (WSIS_OPF_LP; with WSIS_OPF_LP_TRAIN the forms of a training pass): what the executor runs, and why it
+// refuses the rest
 inline bool is_lp(const wsis_op& op) { return (op.flags & WSIS_OPF_LP) != 0; }
-inline bool is_lp_conv(const wsis_op& op) { return op.kind == WSIS_OP_CONV && is_lp(op); }
-// 16-bit B^T weights [K, Cout, Cin] of a 16-bit convolution in the call's workspace
+// ops with 16-bit weights in the call's workspace: B^T [K, Cout, Cin] of a forward convolution, the plain cast
+// [K, Cin, Cout] of a backward op that has a dIn product
+inline bool is_lp_conv(const wsis_op& op) {
+  return is_lp(op) && (op.kind == WSIS_OP_CONV || (op.kind == WSIS_OP_CONV_BWD && op.out[0]));
+}
 inline int64_t lp_wt_bytes_of(const wsis_op& op) { return up((int64_t)op.K * op.Cin * op.Cout * 2); }
+inline bool lp_below_2g(int64_t rows, int C) { return rows * C * 2 < ((int64_t)1 << 31); }
 // nullptr: op is not flagged or the executor runs it; otherwise why not
 const char* lp_refusal(const wsis_op& op) {
   if (op.kind == WSIS_OP_CAST_LP && !is_lp(op)) return "CAST_LP without WSIS_OPF_LP (its dtype)";
-  if (!is_lp(op)) return nullptr;
+  if (!is_lp(op)) return (op.flags & WSIS_OPF_LP_TRAIN) ? "WSIS_OPF_LP_TRAIN without WSIS_OPF_LP" : nullptr;
+  // the forms of a training pass (batch statistics, every backward op) run only in a list recorded as one: an inference
+  // list (section 10.1 of DESIGN.md) that holds one of them is a recording error and is refused as before
+  const bool train_form = (op.kind == WSIS_OP_BN_RELU && (op.flags & WSIS_OPF_TRAINING)) || op.kind == WSIS_OP_BN_RELU_BWD ||
+                          op.kind == WSIS_OP_CONV_BWD || op.kind == WSIS_OP_SPLIT;
+  if (train_form && !(op.flags & WSIS_OPF_LP_TRAIN))
+    return "16-bit training form (training BatchNorm, CONV_BWD, BN_RELU_BWD, SPLIT) without WSIS_OPF_LP_TRAIN";
   if (op.reserved != 0 && op.reserved != 1) return "16-bit op with a dtype other than 0 (bf16) or 1 (fp16)";
+  if (op.flags & (WSIS_OPF_BN_IN | WSIS_OPF_STAT_FIN | WSIS_OPF_STATS))
+    return "16-bit op with a fused BatchNorm form or epilogue statistics (16-bit passes run every BatchNorm as an op)";
   switch (op.kind) {
     case WSIS_OP_CONV:
-      if (op.flags & (WSIS_OPF_BN_IN | WSIS_OPF_STAT_FIN | WSIS_OPF_STATS))
-        return "16-bit convolution with a fused BatchNorm form or statistics (inference passes apply BatchNorm as an op)";
       if (!wsis_spconv_lp_supported(op.K, op.Cin, op.Cout))
         return "16-bit convolution outside wsis_spconv_lp_supported (channels multiples of 32, at most 512)";
       if (op.M_in * op.Cin * 2 >= ((int64_t)1 << 31)) return "16-bit convolution input of 2 GiB or more";
       if (!op.in[3]) return "16-bit convolution without weights";
       return nullptr;
     case WSIS_OP_BN_RELU:
-      if (op.flags & (WSIS_OPF_TRAINING | WSIS_OPF_UPDATE_RUNNING | WSIS_OPF_STATS))
-        return "16-bit BatchNorm in training form (the 16-bit pass is evaluation-mode only: running statistics)";
-      if (!op.in[3] || !op.in[4] || !op.out[0]) return "16-bit BatchNorm without running statistics or output";
+      if (!op.out[0]) return "16-bit BatchNorm without output";
+      if (op.flags & WSIS_OPF_TRAINING) {
+        if (!op.out[1] || !op.out[2]) return "16-bit training BatchNorm without mean / var outputs";
+        if (op.Cin % 8 != 0 || op.Cin > 1024) return "16-bit training BatchNorm outside C % 8 == 0, C <= 1024";
+        if ((op.flags & WSIS_OPF_UPDATE_RUNNING) && (!op.in[3] || !op.in[4]))
+          return "16-bit BatchNorm updates running statistics it does not have";
+        return nullptr;
+      }
+      if (op.flags & WSIS_OPF_UPDATE_RUNNING) return "16-bit evaluation BatchNorm with WSIS_OPF_UPDATE_RUNNING";
+      if (!op.in[3] || !op.in[4]) return "16-bit evaluation BatchNorm without running statistics";
+      return nullptr;
+    case WSIS_OP_BN_RELU_BWD:
+      if (op.Cin % 8 != 0 || op.Cin > 1024) return "16-bit BatchNorm backward outside C % 8 == 0, C <= 1024";
+      if (!op.in[0] || !op.in[1] || !op.in[2] || !op.in[3] || !op.out[1] || !op.out[2])
+        return "16-bit BatchNorm backward without x, dy, statistics or parameter-gradient outputs";
       return nullptr;
     case WSIS_OP_CAT:
-      if ((op.Cin | op.Cout) & 1) return "16-bit concatenation of an odd channel count";
+    case WSIS_OP_SPLIT:
+      if ((op.Cin | op.Cout) & 1) return "16-bit concatenation / split of an odd channel count";
       return nullptr;
     case WSIS_OP_CAST_LP:
       return nullptr;
     case WSIS_OP_CONV_BWD:
-    case WSIS_OP_BN_RELU_BWD:
-      return "16-bit backward op (the 16-bit pass is inference only)";
+      if (!op.in[0] || !op.in[2]) return "16-bit backward convolution without X or dY";
+      if (!lp_below_2g(op.M_out, op.Cout)) return "16-bit backward convolution with a dY of 2 GiB or more";
+      if (op.out[0]) {      // dIn gathers dY: the roles of the channel counts swap
+        if (!wsis_spconv_lp_supported(op.K, op.Cout, op.Cin))
+          return "16-bit dIn product outside wsis_spconv_lp_supported (channels multiples of 32, at most 512)";
+        if (!op.in[1]) return "16-bit dIn product without weights";
+      }
+      if (op.out[1] && (!wsis_spconv_lp_supported(op.K, op.Cin, op.Cout) || !lp_below_2g(op.M_in, op.Cin)))
+        return "16-bit weight gradient outside wsis_spconv_lp_supported or with an input of 2 GiB or more";
+      return nullptr;
     default:
       return "16-bit form of an op kind that has none";
   }
@@ -410,6 +457,7 @@ const char* lp_refusal(const wsis_op& op) {
 
 // slab workspace of an op's weight-gradient product (the own-rows form when its input BatchNorm is applied on the fly)
 inline int64_t dw_ws_of(const wsis_op& op) {
+  if (is_lp(op)) return up(wsis_spconv_dw_lp_workspace_bytes(op.M_out, op.K, op.Cin, op.Cout));
   if (op.flags & WSIS_OPF_BN_IN) return up(wsis_spconv_dw_bn_workspace_bytes(op.M_in, op.K, op.Cin, op.Cout));
   return up(wsis_spconv_dw_workspace_bytes(op.M_out, op.K, op.Cin, op.Cout));
 }
@@ -437,6 +485,7 @@ int64_t op_ws_bytes(const wsis_op& op, bool on) {
                          wsis_bn_stats_finalize_workspace_bytes((op.M_in + 31) / 32, op.Cin)));
     case WSIS_OP_CONV_BWD:     // the transposed weights and the dW slabs live in their own regions, not here
       if (!op.out[0]) return 0;
+      if (is_lp(op)) return up(wsis_spconv_fwd_lp_workspace_bytes(op.M_in, op.K, op.Cout, op.Cin));
       if (use_fwd2(op, on)) return up(wsis_spconv_fwd_t_workspace_bytes(op.M_in, op.K, op.Cout, op.Cin));
       return up(wsis_spconv_fwd_workspace_bytes(op.M_in, op.K, op.Cout, op.Cin));
     default:
@@ -970,7 +1019,8 @@ int launch_weight_batches(const wsis_op* ops, int n, const std::vector<int64_t>&
     b.K[b.n] = op.K;
     b.Cin[b.n] = op.Cin;
     b.Cout[b.n] = op.Cout;
-    b.flip[b.n] = ((lp || !fwd) && (op.flags & WSIS_OPF_FLIP)) ? 1 : 0;
+    b.plain[b.n] = (lp && !fwd) ? 1 : 0;      // (a 16-bit dIn product takes slice K-1-k itself: wsis_spconv_fwd_lp flip)
+    b.flip[b.n] = (!b.plain[b.n] && (lp || !fwd) && (op.flags & WSIS_OPF_FLIP)) ? 1 : 0;
     b.start[b.n + 1] = b.start[b.n] + op.K * ((op.Cin + WT_TILE - 1) / WT_TILE) * ((op.Cout + WT_TILE - 1) / WT_TILE);
     ++b.n;
   }
@@ -1196,11 +1246,21 @@ int bn_training_stats(PassRun& r, const wsis_op& op, int i, bool* applied) {
 }
 
 int bn_relu_launches(PassRun& r, const wsis_op& op, int i) {
-  if (is_lp(op))      // evaluation form: the running statistics, 16-bit x, 16-bit (or fp32) y
-    return wsis_bn_apply_lp(op.in[0], (const float*)op.in[3], (const float*)op.in[4], (const float*)op.in[1],
-                            (const float*)op.in[2], op.eps, relu_of(op), op.out[0], (op.flags & WSIS_OPF_OUT_F32) ? 1 : 0,
-                            op.M_in, op.Cin, op.reserved, r.stream);
   const bool training = (op.flags & WSIS_OPF_TRAINING) != 0;
+  if (is_lp(op)) {      // 16-bit x, 16-bit (or fp32) y; fp32 statistics: the running ones, or those of this batch first
+    if (training) {
+      if (op.M_in <= 0) return WSIS_OK;      // (an empty level: nothing to reduce, nothing to store)
+      const bool upd = (op.flags & WSIS_OPF_UPDATE_RUNNING) != 0;
+      const int rc = wsis_bn_stats_lp(op.in[0], op.M_in, op.Cin, (float*)op.out[1], (float*)op.out[2],
+                                      upd ? (float*)op.in[3] : nullptr, upd ? (float*)op.in[4] : nullptr, op.momentum, r.ws,
+                                      r.ws_bytes, op.reserved, r.stream);
+      if (rc != WSIS_OK) return rc;
+    }
+    return wsis_bn_apply_lp(op.in[0], (const float*)(training ? op.out[1] : op.in[3]),
+                            (const float*)(training ? op.out[2] : op.in[4]), (const float*)op.in[1], (const float*)op.in[2],
+                            op.eps, relu_of(op), op.out[0], (op.flags & WSIS_OPF_OUT_F32) ? 1 : 0, op.M_in, op.Cin,
+                            op.reserved, r.stream);
+  }
   if (training) {
     bool applied = false;
     const int rc = bn_training_stats(r, op, i, &applied);
@@ -1255,12 +1315,17 @@ int issue_cast_lp(PassRun& r, const wsis_op& op, int) {
 
 int issue_split(PassRun& r, const wsis_op& op, int) {
   if (op.M_in <= 0) return WSIS_OK;
-  if (vec4_ok(op, op.in[0], op.out[0], op.out[1]))
-    hipLaunchKernelGGL(split_rows_kernel<4>, dim3(grid_for(op.M_in * (op.Cin + op.Cout) / 4, 256)), dim3(256), 0, r.st,
-                       (const float*)op.in[0], (float*)op.out[0], (float*)op.out[1], op.M_in, op.Cin, op.Cout);
+  wsis_op c = op;      // (16-bit: 4-byte words of halved channel counts, as issue_cat)
+  if (is_lp(op)) {
+    c.Cin /= 2;
+    c.Cout /= 2;
+  }
+  if (vec4_ok(c, c.in[0], c.out[0], c.out[1]))
+    hipLaunchKernelGGL(split_rows_kernel<4>, dim3(grid_for(c.M_in * (c.Cin + c.Cout) / 4, 256)), dim3(256), 0, r.st,
+                       (const float*)c.in[0], (float*)c.out[0], (float*)c.out[1], c.M_in, c.Cin, c.Cout);
   else
-    hipLaunchKernelGGL(split_rows_kernel<1>, dim3(grid_for(op.M_in * (op.Cin + op.Cout), 256)), dim3(256), 0, r.st,
-                       (const float*)op.in[0], (float*)op.out[0], (float*)op.out[1], op.M_in, op.Cin, op.Cout);
+    hipLaunchKernelGGL(split_rows_kernel<1>, dim3(grid_for(c.M_in * (c.Cin + c.Cout), 256)), dim3(256), 0, r.st,
+                       (const float*)c.in[0], (float*)c.out[0], (float*)c.out[1], c.M_in, c.Cin, c.Cout);
   return launch_status();
 }
 
@@ -1277,6 +1342,9 @@ int issue_din(PassRun& r, const wsis_op& op, int i) {
   const int32_t *nbr = (const int32_t*)op.in[5], *order = (const int32_t*)op.in[6];
   float* dX = (float*)op.out[0];
   const bool stats = (op.flags & WSIS_OPF_STATS) != 0;
+  if (is_lp(op))      // 16-bit dY and dX; the weight was rounded where it stands at the top of the call (plan.lp_off)
+    return wsis_spconv_fwd_lp(op.in[2], nbr, order, r.region(PassPlan::LP) + r.plan.lp_off[i], flip_of(op), nullptr, op.out[0],
+                              op.M_out, op.M_in, op.K, op.Cout, op.Cin, op.reserved, r.ws, r.ws_bytes, r.stream);
   if (r.plan.wt_off[i] >= 0) {
     if (stats)
       return fail(WSIS_ERR_ARG, "op %d: BatchNorm partials requested from a dIn pass that is not on wsis_spconv_fwd_t", i);
@@ -1319,7 +1387,14 @@ int issue_conv_bwd(PassRun& r, const wsis_op& op, int i) {
 int issue_bn_relu_bwd(PassRun& r, const wsis_op& op, int i) {
   ProfScope prof(2, r.st);      // (see issue_bn_relu)
   int rc;
-  if ((op.flags & WSIS_OPF_STATS) && !r.bn_unfused[i]) {      // the producing dIn pass left the slice partials in in[7]
+  if (is_lp(op)) {
+    rc = op.M_in <= 0 ? WSIS_OK
+                      : wsis_bn_bwd_lp(op.in[0], op.in[1], (const float*)op.in[2], (const float*)op.in[3],
+                                       (const float*)op.in[4], (const float*)op.in[5], op.eps, relu_of(op),
+                                       (op.flags & WSIS_OPF_TRAINING) ? 1 : 0, op.out[0], (op.flags & WSIS_OPF_OUT_F32) ? 1 : 0,
+                                       (float*)op.out[1], (float*)op.out[2], op.in[6], op.M_in, op.Cin, op.reserved, r.ws,
+                                       r.ws_bytes, r.stream);
+  } else if ((op.flags & WSIS_OPF_STATS) && !r.bn_unfused[i]) {      // the producing dIn pass left the slice partials in in[7]
     if (!op.in[7] || !(op.flags & WSIS_OPF_TRAINING))
       rc = fail(WSIS_ERR_ARG, "op %d: BatchNorm backward from partials needs in[7] and training mode", i);
     else

@@ -143,7 +143,23 @@ class Network(nn.Module):
                                           lambda: unet_native.lp_bn_eval(self),
                                           lambda: unet_native.lp_in_domain(self, int(input.features.shape[0]))):
                 self.last_pass = "native_lp"
-        if self.last_pass == "native_lp":
+        # ... and a training pass in 16 bits with WSIS_NATIVE_LP_TRAIN=1: the 16-bit native forward + backward
+        # (unet_native.lp_train_pass_wanted)
+        if self.last_pass == "modules" and lp_dtype is not None and os.environ.get("WSIS_NATIVE_LP_TRAIN", "0") == "1":
+            import unet_native
+            if unet_native.lp_train_pass_wanted(os.environ, lp_dtype, torch.is_grad_enabled(),
+                                                lambda: unet_native.lp_params_fp32(self, input.features.device),
+                                                lambda: unet_native.lp_bn_train(self),
+                                                lambda: unet_native.lp_train_in_domain(self, int(input.features.shape[0])),
+                                                lambda: wsis_parallel.sync_batchnorm_active(self)):
+                self.last_pass = "native_lp_train"
+        if self.last_pass == "native_lp_train":
+            voxel_feats = unet_native.run_unet_lp_train(
+                self, input, lp_dtype, unet_native.lp_out_dtype(lp_dtype, torch.is_autocast_enabled("cuda")))
+            if branch is not None:
+                for gconv in self.ecc.gconvs:
+                    gconv.prefetch_filter_state(branch, params_ready)
+        elif self.last_pass == "native_lp":
             voxel_feats = unet_native.run_unet_lp(self, input, lp_dtype,
                                                   unet_native.lp_out_dtype(lp_dtype, torch.is_autocast_enabled("cuda")))
             if branch is not None:

@@ -18,10 +18,12 @@ Activations live in one arena per pass (bump allocation, nothing is freed before
 rematerialisation pointless at these sizes), parameter gradients densely in one flat buffer whose views become
 ``p.grad`` (and which ``parallel.GradSync`` all-reduces in place).
 
-The training op list is fp32 only: ``Network.forward`` takes this pass for fp32 features outside autocast.  For 16-bit
-features or under ``torch.autocast`` (spconv.ops.compute_dtype) it walks the modules -- except for an evaluation-mode
-forward without gradients with WSIS_NATIVE_LP=1 (``lp_pass_wanted``), which runs the 16-bit forward program of
-``UNetProgram.compiled_lp`` (``run_unet_lp``).
+``Network.forward`` takes the fp32 pass for fp32 features outside autocast.  For 16-bit features or under
+``torch.autocast`` (spconv.ops.compute_dtype) it walks the modules -- except for an evaluation-mode forward without
+gradients with WSIS_NATIVE_LP=1 (``lp_pass_wanted``), which runs the 16-bit forward program of
+``UNetProgram.compiled_lp`` (``run_unet_lp``), and a training-mode pass with
+WSIS_NATIVE_LP_TRAIN=1 (``lp_train_pass_wanted``), which runs the 16-bit forward + backward programs of
+``UNetProgram.compiled_lp_train`` (``_LpTrainEmitter``, ``UNetLpTrainFunction``).
 """
 import collections
 import os
@@ -41,6 +43,8 @@ F_RELU, F_TRAINING, F_UPDATE, F_FLIP, F_STATS, F_BN_IN, F_STAT_FIN = 1, 2, 4, 8,
 N_IN, N_OUT = 12, 8
 OP_CAST_LP = 8
 F_LP, F_OUT_F32 = 128, 256      # 16-bit op (dtype code in wsis_op.reserved); fp32 output of a 16-bit BatchNorm op
+F_LP_TRAIN = 512                # with F_LP: op of a 16-bit TRAINING pass (training BatchNorm and the backward forms need it)
+_LPT = F_LP | F_LP_TRAIN
 
 OP_DTYPE = np.dtype([("kind", "<i4"), ("flags", "<i4"), ("M_in", "<i8"), ("M_out", "<i8"), ("K", "<i4"),
                      ("Cin", "<i4"), ("Cout", "<i4"), ("reserved", "<i4"), ("eps", "<f4"), ("momentum", "<f4"),
@@ -447,6 +451,83 @@ class _LpEmitter(object):
         return cat, None
 
 
+class _LpTrainEmitter(object):
+    """the 16-bit training pass (F_LP | F_LP_TRAIN ops, forward and backward): activations and their gradients are C / 2 floats per
+    row as in ``_LpEmitter``, every BatchNorm is an op of its own that takes its batch statistics in fp32 from the 16-bit x
+    (no virtual handles, no epilogue partials), parameter gradients are fp32 in the same flat buffer as the fp32 pass's.
+    ``conv`` / ``bn_relu`` / ``cat`` return (out_handle, backward_closure) as ``_TrainEmitter`` does.  ``f32_dx_of``: the
+    handle whose gradient leaves the 16-bit domain (the rounded output of the fp32 input convolution): the BatchNorm
+    backward that produces it stores fp32."""
+
+    def __init__(self):
+        self.rec, self.recb, self.prec = _Recorder(_FWD), _Recorder(_BWD), _Recorder(_PAR, align=16)
+        self.grad, self.count = {}, []
+        self.f32_dx_of = 0
+
+    grad_handle = _TrainEmitter.grad_handle
+
+    def conv(self, x, conv, table, lvl_in, lvl_out, residual=0, stats=True):
+        rec, recb = self.rec, self.recb
+        K, Cin, Cout = _conv_dims(conv)
+        W = conv.weight
+        t = table if table is not None else _Table()
+        y = rec.alloc(lvl_out, Cout // 2)
+        rec.op(OP_CONV, _LPT, _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
+               inp=(x, t.nbr_f, t.order_f, W.data_ptr(), 0, residual), out=(y,))
+
+        def bwd(dy):
+            # dIn rounded once from its fp32 accumulators; dW fp32 straight into the flat gradient buffer.  As in the fp32
+            # pass the program does not depend on requires_grad (one recording serves every setting): a frozen weight's
+            # product still runs and _GradArena hands out no view of its slot
+            dx = recb.alloc(lvl_in, Cin // 2)
+            recb.op(OP_CONV_BWD, _LPT | (F_FLIP if t.flip else 0), _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
+                    inp=(x, W.data_ptr(), dy, t.nbr_f, t.order_f, t.nbr_b, t.order_b), out=(dx, self.grad_handle(W)))
+            return dx
+        return y, bwd
+
+    def bn_relu(self, x, bn, lvl, relu=True, fuse=False, out=0, out_f32=False):
+        """``out``: a tensor of the caller's instead of an allocation of the arena; ``out_f32``: y stored as fp32"""
+        rec, recb = self.rec, self.recb
+        C = bn.num_features
+        training = bn.training or not bn.track_running_stats
+        update = bn.training and bn.track_running_stats
+        flags = _LPT | (F_RELU if relu else 0) | (F_TRAINING if training else 0)
+        if update and bn.num_batches_tracked is not None:
+            assert bn.momentum is not None, "cumulative-average BatchNorm is not used by 3D-WSIS"
+            self.count.append(bn)
+        momentum = bn.momentum if bn.momentum is not None else 0.1
+        mean = rec.alloc(-1, C) if training else bn.running_mean.data_ptr()
+        var = rec.alloc(-1, C) if training else bn.running_var.data_ptr()
+        y = out or rec.alloc(lvl, C if out_f32 else C // 2)
+        rec.op(OP_BN_RELU, flags | (F_UPDATE if update else 0) | (F_OUT_F32 if out_f32 else 0), _lvl(lvl), _lvl(lvl), 0, C, C,
+               bn.eps, momentum,
+               inp=(x, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var)),
+               out=(y, mean, var) if training else (y,))
+
+        def bwd(dy, addend=0):
+            # the skip gradient is added in fp32 before the ONE rounding of dx (the walk adds two rounded tensors)
+            f32 = x == self.f32_dx_of
+            dx = recb.alloc(lvl, C if f32 else C // 2)
+            dg = self.grad_handle(bn.weight) if bn.weight is not None else recb.alloc(-1, C)
+            db = self.grad_handle(bn.bias) if bn.bias is not None else recb.alloc(-1, C)
+            recb.op(OP_BN_RELU_BWD, flags | (F_OUT_F32 if f32 else 0), _lvl(lvl), _lvl(lvl), 0, C, C, bn.eps, 0.0,
+                    inp=(x, dy, mean, var, _ptr(bn.weight), _ptr(bn.bias), addend), out=(dx, dg, db))
+            return dx
+        return y, bwd
+
+    def cat(self, a, b, lvl, C0):
+        rec, recb = self.rec, self.recb
+        cat = rec.alloc(lvl, C0)                       # 2 * C0 16-bit channels
+        rec.op(OP_CAT, _LPT, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(a, b), out=(cat,))
+
+        def bwd(d):
+            d_a = recb.alloc(lvl, C0 // 2)
+            d_b = recb.alloc(lvl, C0 // 2)
+            recb.op(OP_SPLIT, _LPT, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(d,), out=(d_a, d_b))
+            return d_a, d_b
+        return cat, bwd
+
+
 # ---- the one walk of the module tree: ``em`` is an emitter, every step returns (out_handle, backward_closure); what the
 # closures do -- and whether anybody calls them -- is the emitter's business (the 16-bit program has no backward)
 def _residual_block(em, x, blk, lvl):
@@ -566,6 +647,51 @@ class UNetProgram(object):
         c.fwd, c.fwd_arena = _Template(rec), _Arena(rec)
         c.fwd.arr["reserved"] = np.where((c.fwd.arr["flags"] & F_LP) != 0, sp_ops._LP_DTYPES[dtype], 0)
         c.out_channels = net.output_layer[0].num_features
+        return c
+
+    def compiled_lp_train(self, dtype, out_f32, need_dx):
+        """the 16-bit training programs (forward + backward) of ``dtype``; ``out_f32``: the output layer's
+        BatchNorm+ReLU stores fp32; ``need_dx``: the input features take a gradient"""
+        key = ("lp_train", dtype, bool(out_f32), bool(need_dx), tuple(bn.training for bn in self.bns),
+               tuple((p.data_ptr(), p.dtype) for p in self.params),
+               tuple((_ptr(bn.running_mean), _ptr(bn.running_var)) for bn in self.bns))
+        return self._cached(key, lambda: self._record_lp_train(dtype, out_f32, need_dx))
+
+    def _record_lp_train(self, dtype, out_f32, need_dx):
+        net = self.net
+        if not lp_params_fp32(net, net.input_conv[0].weight.device):
+            raise ValueError("the 16-bit native pass reads the model's parameters and running statistics as contiguous "
+                             "fp32 tensors (lp_params_fp32); a model with 16-bit parameters walks the modules")
+        em = _LpTrainEmitter()
+        rec, recb = em.rec, em.recb
+        # boundary, forward as _record_lp: the fp32 input convolution on the rounded-and-widened features (external slot
+        # 0), its output rounded once; the output layer writes the caller's tensor (external slot 1)
+        conv0 = net.input_conv[0]
+        K0, Cin0, C0 = _conv_dims(conv0)
+        t0 = _subm(0)
+        W0 = conv0.weight.data_ptr()
+        y32 = rec.alloc(0, C0)
+        rec.op(OP_CONV, 0, _lvl(0), _lvl(0), K0, Cin0, C0, inp=(_EXT | 0, t0.nbr_f, t0.order_f, W0, 0, 0), out=(y32,))
+        y = em.f32_dx_of = rec.alloc(0, C0 // 2)
+        rec.op(OP_CAST_LP, _LPT, _lvl(0), _lvl(0), 0, C0, C0, inp=(y32,), out=(y,))
+        u, b_u = _ublock(em, y, net.unet, 0)
+        _, b_out = em.bn_relu(u, net.output_layer[0], 0, out=_EXT | 1, out_f32=out_f32)
+        # backward: external slot 1 is the incoming gradient in ``dtype``; the rounding is straight-through, so the fp32
+        # dx of the first block's BatchNorm is the dY of the fp32 input convolution
+        d32 = b_u(b_out(_EXT | 1))
+        assert recb.ops[-1].kind == OP_BN_RELU_BWD and recb.ops[-1].flags & F_OUT_F32 and recb.ops[-1].out[S_BN_BWD.DX] == d32
+        dx = recb.alloc(0, Cin0) if need_dx else 0
+        recb.op(OP_CONV_BWD, F_FLIP, _lvl(0), _lvl(0), K0, Cin0, C0,
+                inp=(_EXT | 0, W0, d32, t0.nbr_f, t0.order_f, t0.nbr_b, t0.order_b), out=(dx, em.grad_handle(conv0.weight)))
+        c = types.SimpleNamespace()
+        c.fwd, c.bwd = _Template(rec), _Template(recb)
+        for t in (c.fwd, c.bwd):
+            t.arr["reserved"] = np.where((t.arr["flags"] & F_LP) != 0, sp_ops._LP_DTYPES[dtype], 0)
+        c.fwd_arena, c.bwd_arena, c.par_arena = _Arena(rec), _Arena(recb), _Arena(em.prec)
+        c.dx_id = (dx & _ID_MASK) if need_dx else -1
+        c.grad_ids = [(em.grad[id(p)] & _ID_MASK) if id(p) in em.grad else -1 for p in self.params]
+        c.count = em.count
+        c.in_channels, c.out_channels = Cin0, net.output_layer[0].num_features
         return c
 
     def _mode_key(self, need_dx):
@@ -691,6 +817,18 @@ class _GradArena(object):
     def key_of(prog, c, ptotal, tail, dev):
         return (id(c), int(ptotal), int(tail), dev, tuple(p.requires_grad for p in prog.params))
 
+    @staticmethod
+    def of_pass(prog, c, poffs, ptotal, dev):
+        """the program's own gradient buffer while no parameter still holds a gradient (zero_grad(set_to_none=True), the
+        reference's loop); otherwise (gradient accumulation, a second backward pass) a buffer of this pass's own"""
+        tail = int(prog.tail_floats) * 4
+        ga = prog._garena
+        if ga is None or ga.key != _GradArena.key_of(prog, c, ptotal, tail, dev):
+            ga = prog._garena = _GradArena(prog, c, poffs, ptotal, tail, dev)
+        if not prog.persistent_grads or any(p.grad is not None for p in ga.params):
+            ga = _GradArena(prog, c, poffs, ptotal, tail, dev)
+        return ga
+
     def __init__(self, prog, c, poffs, ptotal, tail, dev):
         self.key = self.key_of(prog, c, ptotal, tail, dev)
         self.c = c                                   # (keeps id(c) from being reused while this buffer lives)
@@ -755,14 +893,7 @@ class UNetFunction(Function):
         boffs, btotal = c.bwd_arena.layout(Mvec)
         poffs, ptotal = c.par_arena.layout(Mvec)
         garena, gbase = _arena_tensor(btotal, dev)
-        tail = int(prog.tail_floats) * 4
-        # the program's own gradient buffer while no parameter still holds a gradient (zero_grad(set_to_none=True), the
-        # reference's loop); otherwise (gradient accumulation, a second backward pass) a buffer of this pass's own
-        ga = prog._garena
-        if ga is None or ga.key != _GradArena.key_of(prog, c, ptotal, tail, dev):
-            ga = prog._garena = _GradArena(prog, c, poffs, ptotal, tail, dev)
-        if not prog.persistent_grads or any(p.grad is not None for p in ga.params):
-            ga = _GradArena(prog, c, poffs, ptotal, tail, dev)
+        ga = _GradArena.of_pass(prog, c, poffs, ptotal, dev)
         parena, pflat, first = ga.arena, ga.flat, ga.first
         luts = _luts(ctx.fwd_lut, ctx.table_lut, ctx.x.data_ptr(), d_out.data_ptr(),
                      bwd=boffs.astype(np.uint64) + np.uint64(gbase), par=ga.lut)
@@ -790,6 +921,53 @@ class UNetFunction(Function):
         sp_ops.verify_pending_counts()       # (see forward: the counts of this pass's rulebooks, long written by now)
         return dx, None, None
 
+
+class UNetLpTrainFunction(Function):
+    """the 16-bit training pass beside ``UNetFunction``: features [M0, Cin] -> [M0, m] of ``out_dtype`` through the
+    programs of ``UNetProgram.compiled_lp_train``.  The forward arena (16-bit activations, fp32 batch statistics) lives
+    until the backward pass; parameter gradients are stored as in ``UNetFunction.backward`` (fp32 views of the flat buffer;
+    parameters with ``requires_grad_(False)`` get none); the early all-reduce milestone (``prog.overlap``) is not used."""
+
+    @staticmethod
+    def forward(ctx, x, prog, dtype, out_dtype, anchor=None):
+        _n.require_cuda(x)
+        need_dx = bool(x.requires_grad)
+        x32 = x.detach().to(dtype).float().contiguous()      # what the walk's input convolution reads
+        c = prog.compiled_lp_train(dtype, out_dtype == torch.float32, need_dx)
+        for bn in c.count:
+            wsis_ops._defer_batch_count(bn)
+        Mvec = prog.Mvec
+        offs, total = c.fwd_arena.layout(Mvec)
+        arena, base = _arena_tensor(total, x.device)
+        out = torch.empty((int(Mvec[0]), c.out_channels), dtype=out_dtype, device=x.device)
+        fwd_lut = offs.astype(np.uint64) + np.uint64(base)
+        _run(_n.hip(), c.fwd.instantiate(Mvec, _luts(fwd_lut, prog.table_lut, x32.data_ptr(), out.data_ptr())), x.device)
+        if not (torch.is_grad_enabled() and (need_dx or anchor is not None)):
+            sp_ops.verify_pending_counts()      # (see UNetFunction.forward)
+        ctx.prog, ctx.c, ctx.arena, ctx.fwd_lut, ctx.x32, ctx.dtype, ctx.in_dtype = prog, c, arena, fwd_lut, x32, dtype, x.dtype
+        ctx.Mvec, ctx.table_lut, ctx.keep = Mvec, prog.table_lut, prog.keep
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        prog, c, Mvec = ctx.prog, ctx.c, ctx.Mvec
+        d16 = sp_ops._aligned(d_out.to(ctx.dtype))      # the incoming gradient, cast once
+        dev = d16.device
+        boffs, btotal = c.bwd_arena.layout(Mvec)
+        poffs, ptotal = c.par_arena.layout(Mvec)
+        garena, gbase = _arena_tensor(btotal, dev)
+        ga = _GradArena.of_pass(prog, c, poffs, ptotal, dev)
+        luts = _luts(ctx.fwd_lut, ctx.table_lut, ctx.x32.data_ptr(), d16.data_ptr(),
+                     bwd=boffs.astype(np.uint64) + np.uint64(gbase), par=ga.lut)
+        _run(_n.hip(), c.bwd.instantiate(Mvec, luts), dev)
+        for p, v in zip(ga.params, ga.views):
+            p.grad = v if p.grad is None else p.grad + v
+        prog.flat_grad, prog.flat_params, prog.flat_tail = ga.flat, ga.params, ga.tail
+        dx = None
+        if c.dx_id >= 0:
+            dx = _view(garena, gbase, boffs[c.dx_id], (int(Mvec[0]), c.in_channels)).to(ctx.in_dtype)
+        sp_ops.verify_pending_counts()
+        return dx, None, None, None, None
 
 
 class _BnSync(object):
@@ -1007,6 +1185,22 @@ def lp_pass_wanted(env, compute_dtype, grad_enabled, params_fp32, bn_eval, in_do
     return all(bool(c() if callable(c) else c) for c in (params_fp32, bn_eval, in_domain))
 
 
+def lp_train_pass_wanted(env, compute_dtype, grad_enabled, params_fp32, bn_train, in_domain, synced):
+    """does ``Network.forward`` take the 16-bit native TRAINING pass?  ``env``: the environment (WSIS_NATIVE_LP_TRAIN=1
+    switches it on, WSIS_NATIVE_UNET=0 off), ``compute_dtype`` / ``grad_enabled`` as for ``lp_pass_wanted``; then, each a
+    bool or a callable that returns one: ``synced``: a SyncBatchNorm group is present (the pass has no 16-bit form of the
+    statistics exchange), ``params_fp32`` (``lp_params_fp32``), ``bn_train``: every BatchNorm layer of the UNet in
+    training mode with running statistics (``lp_bn_train``), ``in_domain``: every forward, dIn and dW product inside
+    spconv.ops.lp_supported (``lp_train_in_domain``).  The cheap conditions come first: a callable runs only when
+    everything in front of it holds.  Pure: no device."""
+    if not (env.get("WSIS_NATIVE_LP_TRAIN", "0") == "1" and env.get("WSIS_NATIVE_UNET", "1") != "0"
+            and compute_dtype in (torch.bfloat16, torch.float16) and grad_enabled):
+        return False
+    if bool(synced() if callable(synced) else synced):
+        return False
+    return all(bool(c() if callable(c) else c) for c in (params_fp32, bn_train, in_domain))
+
+
 def _lp_modules(net):
     return [m for mod in (net.unet, net.output_layer) for m in mod.modules()]
 
@@ -1025,6 +1219,24 @@ def lp_bn_eval(net):
     """every BatchNorm layer of unet + output_layer normalises with its running statistics"""
     return all(not m.training and m.track_running_stats and m.running_mean is not None and m.running_var is not None
                for m in _lp_modules(net) if isinstance(m, nn.BatchNorm1d))
+
+
+def lp_bn_train(net):
+    """every BatchNorm layer of unet + output_layer takes batch statistics and updates running ones (channel counts
+    inside the 16-bit BatchNorm kernels' domain)"""
+    return all(m.training and m.track_running_stats and m.running_mean is not None and m.running_var is not None
+               and m.momentum is not None and m.num_features % 8 == 0 and m.num_features <= 1024
+               for m in _lp_modules(net) if isinstance(m, nn.BatchNorm1d))
+
+
+def lp_train_in_domain(net, rows):
+    """every sparse product of a training pass of the UNet inside spconv.ops.lp_supported: forward, dIn (the channel
+    counts swap) and dW (its dY below 2 GiB too); ``rows``: the finest level's row count, an upper bound of every level's"""
+    import spconv
+    return all(sp_ops.lp_supported(K, Cin, Cout, rows) and sp_ops.lp_supported(K, Cout, Cin, rows)
+               and rows * Cout * 2 < (1 << 31)
+               for K, Cin, Cout in ((int(np.prod(m.kernel_size)), m.in_channels, m.out_channels)
+                                    for m in net.unet.modules() if isinstance(m, spconv.conv.SparseConvolution)))
 
 
 def lp_in_domain(net, rows):
@@ -1077,6 +1289,17 @@ def run_unet_lp(net, input_tensor, dtype, out_dtype):
     _run(_n.hip(), c.fwd.instantiate(Mvec, luts), x.device)
     sp_ops.verify_pending_counts()
     return out
+
+
+def run_unet_lp_train(net, input_tensor, dtype, out_dtype):
+    """the 16-bit training pass of input_conv + unet + output_layer: features -> [M0, m] of ``out_dtype`` with a
+    backward pass (``UNetLpTrainFunction``; rounding contract: DESIGN.md section 10.2)"""
+    _check_experimental_switches()
+    prog = _program(net)
+    prog.bn_sync = None
+    prog.bind(input_tensor)
+    anchor = next((p for p in prog.params if p.requires_grad), None)
+    return UNetLpTrainFunction.apply(input_tensor.features, prog, dtype, out_dtype, anchor)
 
 
 def run_unet(net, input_tensor, sync_group=None):

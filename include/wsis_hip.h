@@ -419,6 +419,21 @@ int wsis_bn_apply(const float* d_x, const float* d_mean, const float* d_var, con
 int wsis_bn_apply_lp(const void* d_x, const float* d_mean, const float* d_var, const float* d_gamma,
                      const float* d_beta, float eps, int32_t relu, void* d_y, int32_t out_fp32, int64_t M, int32_t C,
                      int32_t dtype, void* stream);
+/* Training statistics of a 16-bit x [M, C] (dtype 0 = bf16, 1 = fp16): what torch's BatchNorm computes for the half
+ * features of sparse_unet3d.py:128-137 under mixed precision, here with fp32 statistics and running statistics.  The
+ * result is wsis_bn_stats of the widened x BIT FOR BIT: the same kernels instantiated for the element type (same grids,
+ * same reduction tree, same branch by M: one launch up to WSIS_BN_SMALL_ROWS rows, partial + final above).  Workspace:
+ * wsis_bn_workspace_bytes(M, C).  Domain: C % 8 == 0 (rows are multiples of 16 bytes), C <= 1024, x 16-byte aligned. */
+int wsis_bn_stats_lp(const void* d_x, int64_t M, int32_t C, float* d_mean, float* d_var, float* d_running_mean,
+                     float* d_running_var, float momentum, void* d_ws, int64_t ws_bytes, int32_t dtype, void* stream);
+/* wsis_bn_bwd for 16-bit x, dy and (optional) addend, the backward of the same call sites (sparse_unet3d.py:128-137 under
+ * mixed precision): dgamma / dbeta are fp32 and equal wsis_bn_bwd on the widened inputs bit for bit; dx is that call's fp32
+ * dx (addend included) rounded ONCE to nearest even into 16-bit d_dx, or stored unrounded as fp32 when out_fp32.  d_dx may
+ * be NULL.  Domain and workspace as wsis_bn_stats_lp. */
+int wsis_bn_bwd_lp(const void* d_x, const void* d_dy, const float* d_mean, const float* d_var, const float* d_gamma,
+                   const float* d_beta, float eps, int32_t relu, int32_t training, void* d_dx, int32_t out_fp32,
+                   float* d_dgamma, float* d_dbeta, const void* d_addend, int64_t M, int32_t C, int32_t dtype, void* d_ws,
+                   int64_t ws_bytes, void* stream);
 /* backward of the fused BN(+ReLU): dgamma = sum dz*xhat, dbeta = sum dz (dz = dy masked by the ReLU),
  * dx = gamma*rstd*(dz - dbeta/M - xhat*dgamma/M) when training, gamma*rstd*dz otherwise; d_dx may be NULL.
  * d_addend (optional, [M,C]) is added to dx in the same pass: the gradient arriving over the residual skip
@@ -1017,6 +1032,7 @@ int wsis_adamw_step(const void* d_segments, const int32_t* d_blocks, int64_t n_b
  *                M_in = rows of X / dX, M_out = rows of dY     (weight_transpose + wsis_spconv_fwd + wsis_spconv_dw)
  *   BN_RELU_BWD  in: x, dy, mean, var, gamma, beta, addend     out: dx, dgamma, dbeta      (wsis_bn_bwd)
  *   CAST_LP      in: x fp32 [M_in, Cin]                        out: y 16-bit [M_in, Cin]   (round to nearest even)
+ * The 16-bit forms of CONV, BN_RELU, CAT, SPLIT, CONV_BWD and BN_RELU_BWD (WSIS_OPF_LP) are listed below the op kinds.
  * BN ops use M_in rows and Cin channels.  d_ws from wsis_run_ops_workspace_bytes (max over the ops); d_sync: a
  * zero-filled block of wsis_sync_bytes() bytes (may be NULL: multi-launch forms).
  * Streams: everything the caller's later work depends on is ordered on `stream` when the call returns.  Work that the
@@ -1040,20 +1056,31 @@ enum {
  * WSIS_OPF_STAT_FIN on CONV (with WSIS_OPF_STATS): the statistics of the output are finished inside the launch for
  * n = 1 or 2 BatchNorm layers: target 0 = out[2] mean, out[3] var, in[10] running_mean, in[11] running_var, op.momentum;
  * target 1 (when out[4] != NULL) = out[4], out[5], out[6], out[7], op.momentum2. */
-/* WSIS_OPF_LP: a 16-bit op of an evaluation-mode inference pass; op.reserved = dtype (0 = bf16, 1 = fp16).
- *   CONV     wsis_spconv_fwd_lp_res: X, residual (in[5]) and Y in 16 bits.  The 16-bit B^T weights are cast from the fp32
- *            in[3] inside the same call (wsis_weight_cast_lp, transpose = 1; slice K-1-k with WSIS_OPF_FLIP) into the
- *            call's workspace, so the pass follows every optimizer step.  Shape inside wsis_spconv_lp_supported.
- *   BN_RELU  evaluation form only (running statistics in[3], in[4]): wsis_bn_apply_lp, 16-bit x; y in 16 bits, or fp32
- *            with WSIS_OPF_OUT_F32.
- *   CAT      the 16-bit concatenation is the fp32 CAT op with Cin / 2 and Cout / 2 (both even): it copies 4-byte words.
- *   CAST_LP  carries the flag too (its dtype).
- * A flagged op the executor cannot run (training BatchNorm, CONV_BWD, BN_RELU_BWD, a shape outside the 16-bit domain, a
- * fused BatchNorm form) fails the call with WSIS_ERR_ARG before anything is launched.  Lists without the flag run as
- * before. */
+/* WSIS_OPF_LP: a 16-bit op of an inference or training pass; op.reserved = dtype (0 = bf16, 1 = fp16).  Every form is
+ * exactly one single-op entry point (or a fixed sequence of them), so a pass is bit-identical to calling them one by one.
+ * WSIS_OPF_LP_TRAIN (with WSIS_OPF_LP): the op belongs to a 16-bit TRAINING pass.  The forms that only such a pass has --
+ * BN_RELU with WSIS_OPF_TRAINING, BN_RELU_BWD, CONV_BWD, SPLIT -- need it; without it they are refused, so an inference
+ * list that holds one of them by mistake still fails before anything is launched.  The other flagged ops may carry it.
+ *   CONV         wsis_spconv_fwd_lp_res: X, residual (in[5]) and Y in 16 bits.  The 16-bit B^T weights are cast from the
+ *                fp32 in[3] inside the same call (wsis_weight_cast_lp, transpose = 1; slice K-1-k with WSIS_OPF_FLIP) into
+ *                the call's workspace, so the pass follows every optimizer step.  Shape inside wsis_spconv_lp_supported.
+ *   BN_RELU      16-bit x; y in 16 bits, or fp32 with WSIS_OPF_OUT_F32.  Evaluation form (running statistics in[3], in[4]):
+ *                wsis_bn_apply_lp.  With WSIS_OPF_TRAINING (and WSIS_OPF_UPDATE_RUNNING; LP_TRAIN): wsis_bn_stats_lp into out[1] /
+ *                out[2] (fp32), then wsis_bn_apply_lp with them; Cin % 8 == 0.
+ *   BN_RELU_BWD  (LP_TRAIN) wsis_bn_bwd_lp: x, dy, addend in 16 bits, dgamma / dbeta fp32, dx in 16 bits or fp32 with WSIS_OPF_OUT_F32.
+ *   CONV_BWD     (LP_TRAIN) X and dY in 16 bits.  dX (out[0], may be NULL) = wsis_spconv_fwd_lp of dY through nbr_b / order_b with the
+ *                weight cast inside the call (wsis_weight_cast_lp, transpose = 0, no flip; the product takes slice K-1-k
+ *                with WSIS_OPF_FLIP -- the sequence of spconv.ops._backward_lp); dW (out[1], may be NULL) =
+ *                wsis_spconv_dw_lp straight into the fp32 gradient.  Both products inside wsis_spconv_lp_supported, dY below
+ *                2 GiB.  The weight gradients take the same side-stream fork / join plan as the fp32 ones.
+ *   CAT, SPLIT   the fp32 ops with Cin / 2 and Cout / 2 (both even): they copy 4-byte words (SPLIT: LP_TRAIN).
+ *   CAST_LP      carries the flag too (its dtype).
+ * A flagged op the executor cannot run (a training form without WSIS_OPF_LP_TRAIN; WSIS_OPF_STATS, WSIS_OPF_BN_IN or
+ * WSIS_OPF_STAT_FIN on a flagged op; a shape outside the 16-bit domain; ADD) fails the call with WSIS_ERR_ARG before
+ * anything is launched.  Lists without the flag run as before. */
 enum {
   WSIS_OPF_RELU = 1, WSIS_OPF_TRAINING = 2, WSIS_OPF_UPDATE_RUNNING = 4, WSIS_OPF_FLIP = 8, WSIS_OPF_STATS = 16,
-  WSIS_OPF_BN_IN = 32, WSIS_OPF_STAT_FIN = 64, WSIS_OPF_LP = 128, WSIS_OPF_OUT_F32 = 256
+  WSIS_OPF_BN_IN = 32, WSIS_OPF_STAT_FIN = 64, WSIS_OPF_LP = 128, WSIS_OPF_OUT_F32 = 256, WSIS_OPF_LP_TRAIN = 512
 };
 typedef struct wsis_op {
   int32_t kind, flags;
