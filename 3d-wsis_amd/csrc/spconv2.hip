@@ -213,6 +213,28 @@ __global__ __launch_bounds__(256) void spconv2_reduce_stats_kernel(const float4*
   reduce_stats_body<false>(partial, bias, residual, out, M_out, cout4, zs, stats, epi, (int)blockIdx.x, (int)blockIdx.y,
                            (int)gridDim.y, (int)threadIdx.x, sred, sync);
 }
+
+// What the launch decides beyond plan2(), from the plan and the shapes alone (spconv_fwd_t_impl and the plan query
+// wsis_debug_fwd2_plan both call it): the runs of the XCD deal (item_of: band = -xcd_run; 0 = the snake) and whether the
+// one-wave items keep their table entries in registers (TR).
+struct Form2 {
+  bool tr_ok;      // a gather table the TR kernels can hold: row indices the 24-bit multiply covers
+  int TR;          // the launch takes spconv_fwd2_kernel<1, 1, 2, true, ..., TR = true>
+  int xcd_run;
+};
+inline int64_t form2_items(const Plan2& p, int64_t M_out, int Cout) {
+  return ceil_div(M_out, SL) * (Cout / (32 * p.NB)) * p.ZS;
+}
+inline Form2 form2(const Plan2& p, int64_t M_out, int Cout, bool has_table, bool bn_in, int64_t M_in) {
+  Form2 f;
+  // launches of many one-wave items (level 0 of a scene: several rounds of the CUs): runs of 64 items per XCD, so the
+  // gathers of neighbouring slices share an L2 (level 0, 32 -> 32: 56.3 -> 52.7 us, 64 -> 32: 96.0 -> 86.3; with fewer
+  // items per CU the balance of the snake matters more: levels 1-2 measured 0 ... +15 % slower, they keep the snake)
+  f.xcd_run = tune_int("WSIS_FWD2_XCD", (p.NW == 1 && form2_items(p, M_out, Cout) >= 8 * 64 * 8) ? 64 : 0);
+  f.tr_ok = has_table && !bn_in && M_in < ((int64_t)1 << 24) && tune_int("WSIS_FWD2_TR", 1) != 0;
+  f.TR = (f.tr_ok && p.NB == 1 && p.NW == 1 && p.DA == 2 && p.BD) ? 1 : 0;
+  return f;
+}
 }  // namespace
 
 extern "C" {
@@ -343,8 +365,9 @@ static int spconv_fwd_t_impl(const float* d_X, const int32_t* d_nbr, const int32
     }
   }
   hipStream_t st = as_stream(stream);
-  WSIS_REQUIRE(ceil_div(M_out, SL) * (Cout / 32 / p.NB) * p.ZS < ((int64_t)1 << 31), "too many work items");
-  const dim3 grid((unsigned)(ceil_div(M_out, SL) * (Cout / 32 / p.NB) * p.ZS), 1u, 1u);
+  const int64_t n_items = form2_items(p, M_out, Cout);
+  WSIS_REQUIRE(n_items < ((int64_t)1 << 31), "too many work items");
+  const dim3 grid((unsigned)n_items, 1u, 1u);
   static int n_cu = 0;                 // snake period of the item deal (item_of): the CUs of the device
   if (!n_cu) {
     int dev = 0, v = 0;
@@ -352,12 +375,8 @@ static int spconv_fwd_t_impl(const float* d_X, const int32_t* d_nbr, const int32
     WSIS_HIP_CHECK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
     n_cu = v > 0 ? v : 256;
   }
-  // launches of many one-wave items (level 0 of a scene: several rounds of the CUs): runs of 64 items per XCD, so the
-  // gathers of neighbouring slices share an L2 (level 0, 32 -> 32: 56.3 -> 52.7 us, 64 -> 32: 96.0 -> 86.3; with fewer
-  // items per CU the balance of the snake matters more: levels 1-2 measured 0 ... +15 % slower, they keep the snake)
-  const int64_t n_items = ceil_div(M_out, SL) * (Cout / (32 * p.NB)) * p.ZS;
-  const int xcd_run = tune_int("WSIS_FWD2_XCD", (p.NW == 1 && n_items >= 8 * 64 * 8) ? 64 : 0);
-  const int deal_band = xcd_run > 0 ? -xcd_run : tune_int("WSIS_FWD2_SNAKE", 1) ? n_cu : 0x7fffffff;      // (read per call; 0: items in weight order)
+  const Form2 form = form2(p, M_out, Cout, d_nbr != nullptr, bn_in != nullptr, M_in);
+  const int deal_band = form.xcd_run > 0 ? -form.xcd_run : tune_int("WSIS_FWD2_SNAKE", 1) ? n_cu : 0x7fffffff;      // (read per call; 0: items in weight order)
   // WSIS_FWD2_DEAL=1 (read per call; default 0): active offsets dealt round-robin to the waves of a work item instead
   // of ownership by offset index.  Measured neutral on the C2 step (level 1: 1046 -> 1035-1050 us per step, level 2:
   // 855 -> 835) -- the waves of a work item are not what its lifetime waits for -- and it gives up the tile-order
@@ -487,7 +506,6 @@ static int spconv_fwd_t_impl(const float* d_X, const int32_t* d_nbr, const int32
   const int rgh_steps = n_items >= 8 * 64 * 8 ? tune_int("WSIS_FWD2_RGH", 0) & 255 : 0;
   const int rgh_late = (tune_int("WSIS_FWD2_RGH_LATE", 1) && n_items > 16 * n_cu && n_items <= 2 * 16 * n_cu) ? 16 * n_cu : 0;
 #endif
-  const bool tr_ok = d_nbr != nullptr && !bn_in && M_in < ((int64_t)1 << 24) && tune_int("WSIS_FWD2_TR", 1) != 0;
   if (p.NB == 1 && p.DA == 2 && p.BD && (bn_in || p.NW == 16)) {
     switch (p.NW) {
       case 1: WSIS_F2B(1); break;
@@ -506,12 +524,12 @@ static int spconv_fwd_t_impl(const float* d_X, const int32_t* d_nbr, const int32
 #if WSIS_EXPERIMENTAL
       if (p.BD && !bn_in && tune_int("WSIS_FWD2_RG", 0) != 0)
         WSIS_F2RG();
-      else if (p.BD && tr_ok && tune_int("WSIS_FWD2_TR_DA", 2) == 3)
+      else if (p.BD && form.tr_ok && tune_int("WSIS_FWD2_TR_DA", 2) == 3)
         WSIS_F2Y(1, 1, 3, true, false, true);      // the table's 4 KB as a third ring slot: 12 waves per CU, as before
       else
 #endif
 #if WSIS_EXPERIMENTAL
-      if (p.BD && tr_ok && p.ZS == 1 && rgh_steps > 0) {
+      if (p.BD && form.tr_ok && p.ZS == 1 && rgh_steps > 0) {
         const size_t ldsb = (size_t)HDR_TR_BYTES + (size_t)Layout<1, 2, true>::WAVE_BYTES;
         hipExtLaunchKernelGGL((spconv_fwd2h_kernel<false>), grid, dim3(64), (uint32_t)ldsb, st, prof.ka(), prof.kb(), 0u, d_X,
                               d_nbr, d_order, d_WT, d_bias, d_residual, d_out, partial, M_out, K, Cin, Cout,
@@ -519,7 +537,7 @@ static int spconv_fwd_t_impl(const float* d_X, const int32_t* d_nbr, const int32
                               (unsigned long long*)nullptr);
       } else
 #endif
-      if (p.BD && tr_ok)
+      if (form.TR)
         WSIS_F2Y(1, 1, 2, true, false, true);
       else
         WSIS_F2(1, 1, 2);
@@ -573,6 +591,24 @@ int wsis_debug_item_of(int32_t i, int32_t gx, int32_t gy, int32_t gz, int32_t ba
   out3[0] = m.bx;
   out3[1] = m.by;
   out3[2] = m.bz;
+  return 0;
+}
+
+// diagnostic (not part of the ABI header; host only, no GPU call): the launch plan of wsis_spconv_fwd_t /
+// wsis_spconv_fwd_t_bn for a shape, out7 = {NB, NW, ZS, DA, BD, TR, xcd_run} -- plan2() and form2(), the functions the
+// launch itself calls -- for tests/test_fwd2_ref_host.py and tests/test_gpu_fwd2_plans.py
+int wsis_debug_fwd2_plan(int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, int32_t has_table, int64_t M_in,
+                         int32_t* out) {
+  if (!out || M_out < 1 || M_in < 0 || !wsis_spconv_fwd_t_supported(K, Cin, Cout)) return -1;
+  const Plan2 p = plan2(M_out, K, Cin, Cout);
+  const Form2 f = form2(p, M_out, Cout, has_table != 0, false, M_in);
+  out[0] = p.NB;
+  out[1] = p.NW;
+  out[2] = p.ZS;
+  out[3] = p.DA;
+  out[4] = p.BD;
+  out[5] = f.TR;
+  out[6] = f.xcd_run;
   return 0;
 }
 
