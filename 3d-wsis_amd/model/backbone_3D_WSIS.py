@@ -132,48 +132,36 @@ class Network(nn.Module):
         fp32_pass = input.features.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
         self.last_pass = "native" if (input.features.is_cuda and fp32_pass and os.environ.get("WSIS_NATIVE_UNET", "1") != "0"
                                       and (not sync_bn or sync_native)) else "modules"
-        # ... except an evaluation-mode forward without gradients in 16 bits with WSIS_NATIVE_LP=1: the 16-bit native
-        # pass (unet_native.lp_pass_wanted)
+        # ... except where one of the two native 16-bit passes applies: an evaluation-mode forward
+        # without gradients with WSIS_NATIVE_LP=1 (unet_native.lp_pass_wanted), a training pass with
+        # WSIS_NATIVE_LP_TRAIN=1 (unet_native.lp_train_pass_wanted)
         lp_dtype = spconv.ops.compute_dtype(input.features) if input.features.is_cuda else None
-        if self.last_pass == "modules" and lp_dtype is not None and os.environ.get("WSIS_NATIVE_LP", "0") == "1":
+        if self.last_pass == "modules" and lp_dtype is not None and "1" in (os.environ.get("WSIS_NATIVE_LP", "0"),
+                                                                            os.environ.get("WSIS_NATIVE_LP_TRAIN", "0")):
             import unet_native
-            # (the model's conditions as callables: they run only in a no-gradient pass in 16 bits)
-            if unet_native.lp_pass_wanted(os.environ, lp_dtype, torch.is_grad_enabled(),
-                                          lambda: unet_native.lp_params_fp32(self, input.features.device),
-                                          lambda: unet_native.lp_bn_eval(self),
-                                          lambda: unet_native.lp_in_domain(self, int(input.features.shape[0]))):
+            # (the model's conditions as callables: they run only when the switch, the dtype and the gradient mode fit)
+            grad, rows = torch.is_grad_enabled(), int(input.features.shape[0])
+            params_fp32 = lambda: unet_native.lp_params_fp32(self, input.features.device)      # noqa: E731
+            if unet_native.lp_pass_wanted(os.environ, lp_dtype, grad, params_fp32, lambda: unet_native.lp_bn_eval(self),
+                                          lambda: unet_native.lp_in_domain(self, rows)):
                 self.last_pass = "native_lp"
-        # ... and a training pass in 16 bits with WSIS_NATIVE_LP_TRAIN=1: the 16-bit native forward + backward
-        # (unet_native.lp_train_pass_wanted)
-        if self.last_pass == "modules" and lp_dtype is not None and os.environ.get("WSIS_NATIVE_LP_TRAIN", "0") == "1":
-            import unet_native
-            if unet_native.lp_train_pass_wanted(os.environ, lp_dtype, torch.is_grad_enabled(),
-                                                lambda: unet_native.lp_params_fp32(self, input.features.device),
-                                                lambda: unet_native.lp_bn_train(self),
-                                                lambda: unet_native.lp_train_in_domain(self, int(input.features.shape[0])),
-                                                lambda: wsis_parallel.sync_batchnorm_active(self)):
+            elif unet_native.lp_train_pass_wanted(os.environ, lp_dtype, grad, params_fp32, lambda: unet_native.lp_bn_train(self),
+                                                  lambda: unet_native.lp_train_in_domain(self, rows),
+                                                  lambda: wsis_parallel.sync_batchnorm_active(self)):
                 self.last_pass = "native_lp_train"
-        if self.last_pass == "native_lp_train":
-            voxel_feats = unet_native.run_unet_lp_train(
-                self, input, lp_dtype, unet_native.lp_out_dtype(lp_dtype, torch.is_autocast_enabled("cuda")))
-            if branch is not None:
-                for gconv in self.ecc.gconvs:
-                    gconv.prefetch_filter_state(branch, params_ready)
-        elif self.last_pass == "native_lp":
-            voxel_feats = unet_native.run_unet_lp(self, input, lp_dtype,
-                                                  unet_native.lp_out_dtype(lp_dtype, torch.is_autocast_enabled("cuda")))
-            if branch is not None:
-                for gconv in self.ecc.gconvs:
-                    gconv.prefetch_filter_state(branch, params_ready)
-        elif self.last_pass == "native":
+        if self.last_pass != "modules":
             # input_conv -> unet -> output_layer recorded as an op list and issued by one native call per pass
             # (model/unet_native.py); WSIS_NATIVE_UNET=0 walks the modules instead (same kernels, same results)
             import unet_native
-            group = None
-            if sync_native:
-                group = next((wsis_ops.sync_group(m) for m in self.unet.modules()
-                              if isinstance(m, nn.BatchNorm1d) and wsis_ops.sync_group(m) is not None), None)
-            voxel_feats = unet_native.run_unet(self, input, sync_group=group)
+            if self.last_pass == "native":
+                group = None
+                if sync_native:
+                    group = next((wsis_ops.sync_group(m) for m in self.unet.modules()
+                                  if isinstance(m, nn.BatchNorm1d) and wsis_ops.sync_group(m) is not None), None)
+                voxel_feats = unet_native.run_unet(self, input, sync_group=group)
+            else:
+                run_lp = unet_native.run_unet_lp if self.last_pass == "native_lp" else unet_native.run_unet_lp_train
+                voxel_feats = run_lp(self, input, lp_dtype, unet_native.lp_out_dtype(lp_dtype, torch.is_autocast_enabled("cuda")))
             if branch is not None:
                 # issued behind the rulebook build of this pass on the same stream: runs while the UNet does
                 for gconv in self.ecc.gconvs:

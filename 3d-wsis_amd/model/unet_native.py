@@ -11,8 +11,10 @@ so both paths agree bit for bit; what disappears is ~450 Python-dispatched autog
 (sparse_unet3d.py:103-350 walked by torch in the reference).
 
 The walk (``_residual_block`` / ``_ublock``) exists once and emits through ``_TrainEmitter`` (fp32 ops, backward closures,
-everything that lives for one recording) or ``_LpEmitter`` (16-bit forward); ops under construction are ``_Op`` records,
-their pointer slots go by the ``S_*`` names.  tests/test_unet_program_host.py pins the recordings byte for byte on the CPU.
+everything that lives for one recording) or ``_LpEmitter(train)`` (the 16-bit ops: the evaluation forward, or forward and
+backward closures of the training pass); ops under construction are ``_Op`` records, their pointer slots go by the
+``S_*`` names.  ``_record`` and ``_record_lp`` end in ``_program_of``, which sets what every compiled program carries.
+tests/test_unet_program_host.py pins the recordings of all three passes byte for byte on the CPU.
 
 Activations live in one arena per pass (bump allocation, nothing is freed before the backward: 288 GB of HBM make
 rematerialisation pointless at these sizes), parameter gradients densely in one flat buffer whose views become
@@ -23,7 +25,9 @@ rematerialisation pointless at these sizes), parameter gradients densely in one 
 gradients with WSIS_NATIVE_LP=1 (``lp_pass_wanted``), which runs the 16-bit forward program of
 ``UNetProgram.compiled_lp`` (``run_unet_lp``), and a training-mode pass with
 WSIS_NATIVE_LP_TRAIN=1 (``lp_train_pass_wanted``), which runs the 16-bit forward + backward programs of
-``UNetProgram.compiled_lp_train`` (``_LpTrainEmitter``, ``UNetLpTrainFunction``).
+``UNetProgram.compiled_lp_train`` (``UNetLpTrainFunction``).  Both switches go through one rule
+(``_lp_wanted``), and all three passes through one driver: ``_issue_forward`` / ``_issue_backward`` lay out the arenas,
+instantiate and run, ``_store_grads`` hands the gradients to the parameters.
 """
 import collections
 import os
@@ -254,7 +258,17 @@ def _conv_dims(conv):
     return int(np.prod(conv.kernel_size)), conv.in_channels, conv.out_channels
 
 
-class _TrainEmitter(object):
+class _Emitter(object):
+    """what the emitters share: the parameter-gradient handles of one recording (``prec``, ``grad``)"""
+
+    def grad_handle(self, p):
+        # parameter gradients live densely in their own flat buffer (one all-reduce for data parallelism)
+        if id(p) not in self.grad:
+            self.grad[id(p)] = self.prec.alloc(-1, p.numel())
+        return self.grad[id(p)]
+
+
+class _TrainEmitter(_Emitter):
     """the fp32 ops of a training or evaluation pass, with everything that lives for ONE recording: the three recorders,
     the gradient handles, the profiler's entries, the statistics sources and the BatchNorm layers applied by their
     consumer.  ``conv`` / ``bn_relu`` / ``cat`` return (out_handle, backward_closure): a hand-written tape, the closures
@@ -271,12 +285,6 @@ class _TrainEmitter(object):
         self.fuse_fin_lvl = int(os.environ.get("WSIS_FUSE_BN_FIN_LVL", "0"))      # (EXPERIMENTAL build: from this level on)
         if synced:      # every BatchNorm layer stays an op of its own: _run_synced runs it between parts
             self.fuse_fin, self.fuse_apply_lvl = False, 99
-
-    def grad_handle(self, p):
-        # parameter gradients live densely in their own flat buffer (one all-reduce for data parallelism)
-        if id(p) not in self.grad:
-            self.grad[id(p)] = self.prec.alloc(-1, p.numel())
-        return self.grad[id(p)]
 
     def conv(self, x, conv, table, lvl_in, lvl_out, residual=0, stats=True):
         rec, recb = self.rec, self.recb
@@ -418,91 +426,71 @@ class _TrainEmitter(object):
                     break
 
 
-class _LpEmitter(object):
-    """the 16-bit evaluation-mode forward (F_LP ops): a 16-bit activation of C channels is C / 2 floats per row of the
-    arena.  Running statistics only, BatchNorm applied by ops of its own (no statistics, no fused forms), no backward:
-    every closure is None."""
+class _LpEmitter(_Emitter):
+    """the 16-bit ops: a 16-bit activation (or gradient) of C channels is C / 2 floats per row of the arena, every
+    BatchNorm is an op of its own (no virtual handles, no epilogue partials, no fused forms).  ``train`` False: the
+    evaluation-mode forward (F_LP ops), running statistics only, no backward: every closure is None.  ``train`` True: the
+    training pass (F_LP | F_LP_TRAIN ops, forward and backward): a training-mode BatchNorm takes its batch statistics in
+    fp32 from the 16-bit x, parameter gradients are fp32 in the same flat buffer as the fp32 pass's, ``conv`` /
+    ``bn_relu`` / ``cat`` return (out_handle, backward_closure) as ``_TrainEmitter`` does.  ``f32_dx_of``: the handle
+    whose gradient leaves the 16-bit domain (the rounded output of the fp32 input convolution): the BatchNorm backward
+    that produces it stores fp32."""
 
-    def __init__(self):
-        self.rec = _Recorder(_FWD)
-
-    def conv(self, x, conv, table, lvl_in, lvl_out, residual=0, stats=True):
-        K, Cin, Cout = _conv_dims(conv)
-        t = table if table is not None else _Table()
-        y = self.rec.alloc(lvl_out, Cout // 2)
-        # (the executor casts the fp32 weight to 16-bit B^T slices inside the call: the pass follows the optimizer;
-        # a skip path is added in the epilogue before its one rounding -- the walk adds two rounded tensors)
-        self.rec.op(OP_CONV, F_LP, _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
-                    inp=(x, t.nbr_f, t.order_f, conv.weight.data_ptr(), 0, residual), out=(y,))
-        return y, None
-
-    def bn_relu(self, x, bn, lvl, relu=True, fuse=False, out=0, out_f32=False):
-        """``out``: a tensor of the caller's instead of an allocation of the arena; ``out_f32``: stored as fp32"""
-        C = bn.num_features
-        y = out or self.rec.alloc(lvl, C if out_f32 else C // 2)
-        flags = F_LP | (F_RELU if relu else 0) | (F_OUT_F32 if out_f32 else 0)
-        self.rec.op(OP_BN_RELU, flags, _lvl(lvl), _lvl(lvl), 0, C, C, bn.eps, 0.0,
-                    inp=(x, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var)), out=(y,))
-        return y, None
-
-    def cat(self, a, b, lvl, C0):
-        cat = self.rec.alloc(lvl, C0)                  # 2 * C0 16-bit channels
-        self.rec.op(OP_CAT, F_LP, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(a, b), out=(cat,))
-        return cat, None
-
-
-class _LpTrainEmitter(object):
-    """the 16-bit training pass (F_LP | F_LP_TRAIN ops, forward and backward): activations and their gradients are C / 2 floats per
-    row as in ``_LpEmitter``, every BatchNorm is an op of its own that takes its batch statistics in fp32 from the 16-bit x
-    (no virtual handles, no epilogue partials), parameter gradients are fp32 in the same flat buffer as the fp32 pass's.
-    ``conv`` / ``bn_relu`` / ``cat`` return (out_handle, backward_closure) as ``_TrainEmitter`` does.  ``f32_dx_of``: the
-    handle whose gradient leaves the 16-bit domain (the rounded output of the fp32 input convolution): the BatchNorm
-    backward that produces it stores fp32."""
-
-    def __init__(self):
-        self.rec, self.recb, self.prec = _Recorder(_FWD), _Recorder(_BWD), _Recorder(_PAR, align=16)
-        self.grad, self.count = {}, []
-        self.f32_dx_of = 0
-
-    grad_handle = _TrainEmitter.grad_handle
+    def __init__(self, train):
+        self.train, self.lp = train, _LPT if train else F_LP
+        self.rec, self.count, self.f32_dx_of = _Recorder(_FWD), [], 0
+        if train:
+            self.recb, self.prec, self.grad = _Recorder(_BWD), _Recorder(_PAR, align=16), {}
 
     def conv(self, x, conv, table, lvl_in, lvl_out, residual=0, stats=True):
-        rec, recb = self.rec, self.recb
+        rec = self.rec
         K, Cin, Cout = _conv_dims(conv)
         W = conv.weight
         t = table if table is not None else _Table()
         y = rec.alloc(lvl_out, Cout // 2)
-        rec.op(OP_CONV, _LPT, _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
+        # (the executor casts the fp32 weight to 16-bit B^T slices inside the call: the pass follows the optimizer;
+        # a skip path is added in the epilogue before its one rounding -- the walk adds two rounded tensors)
+        rec.op(OP_CONV, self.lp, _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
                inp=(x, t.nbr_f, t.order_f, W.data_ptr(), 0, residual), out=(y,))
+        if not self.train:
+            return y, None
+        recb = self.recb
 
         def bwd(dy):
             # dIn rounded once from its fp32 accumulators; dW fp32 straight into the flat gradient buffer.  As in the fp32
             # pass the program does not depend on requires_grad (one recording serves every setting): a frozen weight's
             # product still runs and _GradArena hands out no view of its slot
             dx = recb.alloc(lvl_in, Cin // 2)
-            recb.op(OP_CONV_BWD, _LPT | (F_FLIP if t.flip else 0), _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
+            recb.op(OP_CONV_BWD, self.lp | (F_FLIP if t.flip else 0), _lvl(lvl_in), _lvl(lvl_out), K, Cin, Cout,
                     inp=(x, W.data_ptr(), dy, t.nbr_f, t.order_f, t.nbr_b, t.order_b), out=(dx, self.grad_handle(W)))
             return dx
         return y, bwd
 
     def bn_relu(self, x, bn, lvl, relu=True, fuse=False, out=0, out_f32=False):
         """``out``: a tensor of the caller's instead of an allocation of the arena; ``out_f32``: y stored as fp32"""
-        rec, recb = self.rec, self.recb
+        rec = self.rec
         C = bn.num_features
-        training = bn.training or not bn.track_running_stats
-        update = bn.training and bn.track_running_stats
-        flags = _LPT | (F_RELU if relu else 0) | (F_TRAINING if training else 0)
+        # (the evaluation program applies the running statistics whatever the layer's mode)
+        training = self.train and (bn.training or not bn.track_running_stats)
+        update = self.train and bn.training and bn.track_running_stats
+        flags = self.lp | (F_RELU if relu else 0) | (F_TRAINING if training else 0)
         if update and bn.num_batches_tracked is not None:
             assert bn.momentum is not None, "cumulative-average BatchNorm is not used by 3D-WSIS"
             self.count.append(bn)
-        momentum = bn.momentum if bn.momentum is not None else 0.1
-        mean = rec.alloc(-1, C) if training else bn.running_mean.data_ptr()
-        var = rec.alloc(-1, C) if training else bn.running_var.data_ptr()
+        # Two differences between the passes that no kernel reads but the byte-identity test
+        # (tests/test_unet_program_host.py) keeps: an op that applies running statistics records momentum 0.0 and
+        # out=(y,) in the evaluation program, the layer's own momentum (0.1 here) in a training pass
+        momentum = (bn.momentum if bn.momentum is not None else 0.1) if self.train else 0.0
+        mean = rec.alloc(-1, C) if training else _ptr(bn.running_mean)
+        var = rec.alloc(-1, C) if training else _ptr(bn.running_var)
         y = out or rec.alloc(lvl, C if out_f32 else C // 2)
         rec.op(OP_BN_RELU, flags | (F_UPDATE if update else 0) | (F_OUT_F32 if out_f32 else 0), _lvl(lvl), _lvl(lvl), 0, C, C,
                bn.eps, momentum,
                inp=(x, _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var)),
                out=(y, mean, var) if training else (y,))
+        if not self.train:
+            return y, None
+        recb = self.recb
 
         def bwd(dy, addend=0):
             # the skip gradient is added in fp32 before the ONE rounding of dx (the walk adds two rounded tensors)
@@ -516,14 +504,16 @@ class _LpTrainEmitter(object):
         return y, bwd
 
     def cat(self, a, b, lvl, C0):
-        rec, recb = self.rec, self.recb
-        cat = rec.alloc(lvl, C0)                       # 2 * C0 16-bit channels
-        rec.op(OP_CAT, _LPT, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(a, b), out=(cat,))
+        cat = self.rec.alloc(lvl, C0)                  # 2 * C0 16-bit channels
+        self.rec.op(OP_CAT, self.lp, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(a, b), out=(cat,))
+        if not self.train:
+            return cat, None
+        recb = self.recb
 
         def bwd(d):
             d_a = recb.alloc(lvl, C0 // 2)
             d_b = recb.alloc(lvl, C0 // 2)
-            recb.op(OP_SPLIT, _LPT, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(d,), out=(d_a, d_b))
+            recb.op(OP_SPLIT, self.lp, _lvl(lvl), _lvl(lvl), 0, C0, C0, inp=(d,), out=(d_a, d_b))
             return d_a, d_b
         return cat, bwd
 
@@ -621,33 +611,7 @@ class UNetProgram(object):
         key = ("lp", dtype, bool(out_f32), tuple((p.data_ptr(), p.dtype) for p in self.params),
                tuple((_ptr(bn.running_mean), _ptr(bn.running_var), bn.running_var.dtype if bn.running_var is not None
                       else None) for bn in self.bns))
-        return self._cached(key, lambda: self._record_lp(dtype, out_f32))
-
-    def _record_lp(self, dtype, out_f32):
-        net = self.net
-        dev = net.input_conv[0].weight.device
-        if not lp_params_fp32(net, dev):
-            raise ValueError("the 16-bit native pass reads the model's parameters and running statistics as contiguous "
-                             "fp32 tensors (lp_params_fp32); a model with 16-bit parameters walks the modules")
-        em = _LpEmitter()
-        rec = em.rec
-        # the 6 -> 32 input convolution lies outside the 16-bit domain: the fp32 op, its output rounded once (what the
-        # module walk's fallback does, spconv.ops._forward_lp)
-        conv0 = net.input_conv[0]
-        K0, Cin0, C0 = _conv_dims(conv0)
-        t0 = _subm(0)
-        y32 = rec.alloc(0, C0)
-        rec.op(OP_CONV, 0, _lvl(0), _lvl(0), K0, Cin0, C0,
-               inp=(_EXT | 0, t0.nbr_f, t0.order_f, conv0.weight.data_ptr(), 0, 0), out=(y32,))
-        y = rec.alloc(0, C0 // 2)
-        rec.op(OP_CAST_LP, F_LP, _lvl(0), _lvl(0), 0, C0, C0, inp=(y32,), out=(y,))
-        y, _ = _ublock(em, y, net.unet, 0)
-        em.bn_relu(y, net.output_layer[0], 0, out=_EXT | 1, out_f32=out_f32)
-        c = types.SimpleNamespace()      # forward + backward templates of one (model, mode)
-        c.fwd, c.fwd_arena = _Template(rec), _Arena(rec)
-        c.fwd.arr["reserved"] = np.where((c.fwd.arr["flags"] & F_LP) != 0, sp_ops._LP_DTYPES[dtype], 0)
-        c.out_channels = net.output_layer[0].num_features
-        return c
+        return self._cached(key, lambda: self._record_lp(dtype, out_f32, False, False))
 
     def compiled_lp_train(self, dtype, out_f32, need_dx):
         """the 16-bit training programs (forward + backward) of ``dtype``; ``out_f32``: the output layer's
@@ -655,17 +619,19 @@ class UNetProgram(object):
         key = ("lp_train", dtype, bool(out_f32), bool(need_dx), tuple(bn.training for bn in self.bns),
                tuple((p.data_ptr(), p.dtype) for p in self.params),
                tuple((_ptr(bn.running_mean), _ptr(bn.running_var)) for bn in self.bns))
-        return self._cached(key, lambda: self._record_lp_train(dtype, out_f32, need_dx))
+        return self._cached(key, lambda: self._record_lp(dtype, out_f32, True, need_dx))
 
-    def _record_lp_train(self, dtype, out_f32, need_dx):
+    def _record_lp(self, dtype, out_f32, train, need_dx):
+        """the 16-bit program(s): the forward alone (``train`` False) or forward + backward"""
         net = self.net
         if not lp_params_fp32(net, net.input_conv[0].weight.device):
             raise ValueError("the 16-bit native pass reads the model's parameters and running statistics as contiguous "
                              "fp32 tensors (lp_params_fp32); a model with 16-bit parameters walks the modules")
-        em = _LpTrainEmitter()
-        rec, recb = em.rec, em.recb
-        # boundary, forward as _record_lp: the fp32 input convolution on the rounded-and-widened features (external slot
-        # 0), its output rounded once; the output layer writes the caller's tensor (external slot 1)
+        em = _LpEmitter(train)
+        rec = em.rec
+        # boundary: the 6 -> 32 input convolution lies outside the 16-bit domain: the fp32 op on the rounded-and-widened
+        # features (external slot 0), its output rounded once (what the module walk's fallback does,
+        # spconv.ops._forward_lp); the output layer writes the caller's tensor (external slot 1)
         conv0 = net.input_conv[0]
         K0, Cin0, C0 = _conv_dims(conv0)
         t0 = _subm(0)
@@ -673,25 +639,40 @@ class UNetProgram(object):
         y32 = rec.alloc(0, C0)
         rec.op(OP_CONV, 0, _lvl(0), _lvl(0), K0, Cin0, C0, inp=(_EXT | 0, t0.nbr_f, t0.order_f, W0, 0, 0), out=(y32,))
         y = em.f32_dx_of = rec.alloc(0, C0 // 2)
-        rec.op(OP_CAST_LP, _LPT, _lvl(0), _lvl(0), 0, C0, C0, inp=(y32,), out=(y,))
+        rec.op(OP_CAST_LP, em.lp, _lvl(0), _lvl(0), 0, C0, C0, inp=(y32,), out=(y,))
         u, b_u = _ublock(em, y, net.unet, 0)
         _, b_out = em.bn_relu(u, net.output_layer[0], 0, out=_EXT | 1, out_f32=out_f32)
-        # backward: external slot 1 is the incoming gradient in ``dtype``; the rounding is straight-through, so the fp32
-        # dx of the first block's BatchNorm is the dY of the fp32 input convolution
-        d32 = b_u(b_out(_EXT | 1))
-        assert recb.ops[-1].kind == OP_BN_RELU_BWD and recb.ops[-1].flags & F_OUT_F32 and recb.ops[-1].out[S_BN_BWD.DX] == d32
-        dx = recb.alloc(0, Cin0) if need_dx else 0
-        recb.op(OP_CONV_BWD, F_FLIP, _lvl(0), _lvl(0), K0, Cin0, C0,
-                inp=(_EXT | 0, W0, d32, t0.nbr_f, t0.order_f, t0.nbr_b, t0.order_b), out=(dx, em.grad_handle(conv0.weight)))
-        c = types.SimpleNamespace()
-        c.fwd, c.bwd = _Template(rec), _Template(recb)
+        dx = 0
+        if train:
+            # backward: external slot 1 is the incoming gradient in ``dtype``; the rounding is straight-through, so the
+            # fp32 dx of the first block's BatchNorm is the dY of the fp32 input convolution
+            recb = em.recb
+            d32 = b_u(b_out(_EXT | 1))
+            assert recb.ops[-1].kind == OP_BN_RELU_BWD and recb.ops[-1].flags & F_OUT_F32 and recb.ops[-1].out[S_BN_BWD.DX] == d32
+            dx = recb.alloc(0, Cin0) if need_dx else 0
+            recb.op(OP_CONV_BWD, F_FLIP, _lvl(0), _lvl(0), K0, Cin0, C0,
+                    inp=(_EXT | 0, W0, d32, t0.nbr_f, t0.order_f, t0.nbr_b, t0.order_b), out=(dx, em.grad_handle(conv0.weight)))
+        c = self._program_of(em, -1, dx if need_dx else -1)
         for t in (c.fwd, c.bwd):
-            t.arr["reserved"] = np.where((t.arr["flags"] & F_LP) != 0, sp_ops._LP_DTYPES[dtype], 0)
-        c.fwd_arena, c.bwd_arena, c.par_arena = _Arena(rec), _Arena(recb), _Arena(em.prec)
-        c.dx_id = (dx & _ID_MASK) if need_dx else -1
-        c.grad_ids = [(em.grad[id(p)] & _ID_MASK) if id(p) in em.grad else -1 for p in self.params]
+            if t is not None:      # the dtype code of every 16-bit op
+                t.arr["reserved"] = np.where((t.arr["flags"] & F_LP) != 0, sp_ops._LP_DTYPES[dtype], 0)
+        return c
+
+    def _program_of(self, em, out, dx):
+        """what every compiled program of one (model, mode) carries: the templates, the three arenas, the ids of the
+        output and of the input's gradient (handles; -1: none), the parameter-gradient ids, the BatchNorm layers whose
+        batch counter a pass advances, the channel counts.  A program without a backward has ``bwd = None``, no backward
+        or parameter arena and no gradient ids."""
+        c = types.SimpleNamespace()
+        c.fwd, c.fwd_arena = _Template(em.rec), _Arena(em.rec)
+        c.bwd = c.bwd_arena = c.par_arena = None
+        c.grad_ids = []
+        if getattr(em, "recb", None) is not None:
+            c.bwd, c.bwd_arena, c.par_arena = _Template(em.recb), _Arena(em.recb), _Arena(em.prec)
+            c.grad_ids = [(em.grad[id(p)] & _ID_MASK) if id(p) in em.grad else -1 for p in self.params]
+        c.out_id, c.dx_id = (h & _ID_MASK if h >= 0 else -1 for h in (out, dx))
         c.count = em.count
-        c.in_channels, c.out_channels = Cin0, net.output_layer[0].num_features
+        c.in_channels, c.out_channels = self.net.input_conv[0].in_channels, self.net.output_layer[0].num_features
         return c
 
     def _mode_key(self, need_dx):
@@ -714,17 +695,12 @@ class UNetProgram(object):
         out, b_out = em.bn_relu(y, net.output_layer[0], 0)
         dx = b_in(b_u(b_out(_EXT | 1)), need_dx)
         em.fuse_bn_bwd()
-        c = types.SimpleNamespace()      # forward + backward templates of one (model, mode)
-        c.fwd, c.bwd = _Template(em.rec), _Template(em.recb)
-        c.fwd_arena, c.bwd_arena, c.par_arena = _Arena(em.rec), _Arena(em.recb), _Arena(em.prec)
-        c.out_id, c.dx_id = out & _ID_MASK, (dx & _ID_MASK) if need_dx else -1
-        c.grad_ids = [(em.grad[id(p)] & _ID_MASK) if id(p) in em.grad else -1 for p in self.params]
-        c.acc_f, c.acc_b, c.count = em.acc_f, em.acc_b, em.count
+        c = self._program_of(em, out, dx if need_dx else -1)
+        c.acc_f, c.acc_b = em.acc_f, em.acc_b
         # milestone of the backward list: the op after which the first ~half of the flat parameter-gradient buffer is
         # final (gradients are allocated in the order the backward pass produces them)
         last = [max([(h & _ID_MASK) + 1 for h in o.out if h & _PAR] or [0]) for o in em.recb.ops]
         c.bwd_grads_done = np.maximum.accumulate(np.array(last, dtype=np.int64))
-        c.out_channels = net.output_layer[0].num_features
         return c
 
     def bind(self, tensor):
@@ -847,6 +823,61 @@ class _GradArena(object):
         self.tail = self.flat[t0:t0 + prog.tail_floats] if prog.tail_floats else None
 
 
+# ---- the pass driver: what the fp32 pass, the 16-bit training pass and the 16-bit evaluation pass do alike.  ``ext0`` /
+# ``ext1``: device pointers of the two external tensors; ``sy``: the _BnSync state of a synced pass
+def _issue_forward(prog, c, ext0, ext1, device, sy=None):
+    """lays out the forward arena of the bound scene and issues the forward program -> (arena, base, offs, fwd_lut)"""
+    for bn in c.count:
+        wsis_ops._defer_batch_count(bn)
+    Mvec = prog.Mvec
+    offs, total = c.fwd_arena.layout(Mvec)
+    arena, base = _arena_tensor(total, device)
+    fwd_lut = offs.astype(np.uint64) + np.uint64(base)
+    ops = c.fwd.instantiate(Mvec, _luts(fwd_lut, prog.table_lut, ext0, ext1))
+    if sy is not None:
+        sy.arenas = [arena]
+        _run_synced(_n.hip(), ops, device, sy)
+    else:
+        _run(_n.hip(), ops, device)
+    return arena, base, offs, fwd_lut
+
+
+def _issue_backward(prog, c, Mvec, fwd_lut, table_lut, ext0, ext1, device, sy=None, arenas=(), overlap=None):
+    """lays out the backward arena, takes the program's parameter-gradient buffer and issues the backward program ->
+    (garena, gbase, boffs, ga).  ``arenas``: the forward pass's, which a synced layer reads; ``overlap``: a
+    wsis_parallel.GradSync whose all-reduce of the first part of the gradient buffer starts inside the pass"""
+    boffs, btotal = c.bwd_arena.layout(Mvec)
+    poffs, ptotal = c.par_arena.layout(Mvec)
+    garena, gbase = _arena_tensor(btotal, device)
+    ga = _GradArena.of_pass(prog, c, poffs, ptotal, device)
+    ops = c.bwd.instantiate(Mvec, _luts(fwd_lut, table_lut, ext0, ext1, bwd=boffs.astype(np.uint64) + np.uint64(gbase),
+                                        par=ga.lut))
+    if sy is not None:
+        sy.arenas = list(arenas) + [garena, ga.arena]
+        _run_synced(_n.hip(), ops, device, sy)
+    elif overlap is not None and overlap.ready() and len(poffs) > 1:
+        # all-reduce of the first part of the gradient buffer starts while the rest of the pass still runs
+        starts = np.append(poffs, ptotal)
+        want = ptotal // 2
+        op_i = int(np.searchsorted(starts[c.bwd_grads_done], want))          # first op with >= half final
+        op_i = min(op_i, len(c.bwd_grads_done) - 2)
+        split = int(starts[c.bwd_grads_done[op_i]]) // 4
+        _run(_n.hip(), ops, device, mark_op=op_i, waiter=overlap.comm_stream_ptr())
+        overlap.early(ga.flat[ga.first:ga.first + split], ga.first + split)
+    else:
+        _run(_n.hip(), ops, device)
+    return garena, gbase, boffs, ga
+
+
+def _store_grads(prog, ga):
+    """``.grad`` of the parameters from the views of the pass's gradient buffer (accumulated into a gradient that is
+    still there) and the data-parallel hook: the gradients of ``flat_params`` are views of ``flat_grad``
+    (parallel.GradSync)"""
+    for p, v in zip(ga.params, ga.views):
+        p.grad = v if p.grad is None else p.grad + v
+    prog.flat_grad, prog.flat_params, prog.flat_tail = ga.flat, ga.params, ga.tail
+
+
 class UNetFunction(Function):
     """features [M0, Cin] -> [M0, m]; ``prog`` is a bound UNetProgram.  Its parameters are NOT inputs of the node:
     ``backward`` stores their gradients (views of the program's flat buffer) in ``.grad`` itself -- what 230
@@ -859,19 +890,9 @@ class UNetFunction(Function):
         x = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.contiguous().float()
         need_dx = bool(x.requires_grad)
         c = prog.compiled(need_dx)
-        for bn in c.count:
-            wsis_ops._defer_batch_count(bn)
         Mvec, table_lut, tensors = prog.Mvec, prog.table_lut, prog.table_tensors
-        offs, total = c.fwd_arena.layout(Mvec)
-        arena, base = _arena_tensor(total, x.device)
-        fwd_lut = offs.astype(np.uint64) + np.uint64(base)
-        luts = _luts(fwd_lut, table_lut, x.data_ptr(), 0)
         sy = prog.bn_sync.new_pass() if prog.bn_sync is not None else None      # row counts / arenas belong to THIS pass
-        if sy is not None:
-            sy.arenas = [arena]
-            _run_synced(_n.hip(), c.fwd.instantiate(Mvec, luts), x.device, sy)
-        else:
-            _run(_n.hip(), c.fwd.instantiate(Mvec, luts), x.device)
+        arena, base, offs, fwd_lut = _issue_forward(prog, c, x.data_ptr(), 0, x.device, sy)
         ctx.sy = sy
         # tables sized from the batch's host-side level counts: the device's own counts are compared inside the SAME
         # pass -- an inference pass right here (its result is used next; the read waits for the rulebook chain on the
@@ -889,34 +910,10 @@ class UNetFunction(Function):
     def backward(ctx, d_out):
         prog, c, Mvec = ctx.prog, ctx.c, ctx.Mvec
         d_out = d_out if (d_out.dtype == torch.float32 and d_out.is_contiguous()) else d_out.contiguous().float()
-        dev = d_out.device
-        boffs, btotal = c.bwd_arena.layout(Mvec)
-        poffs, ptotal = c.par_arena.layout(Mvec)
-        garena, gbase = _arena_tensor(btotal, dev)
-        ga = _GradArena.of_pass(prog, c, poffs, ptotal, dev)
-        parena, pflat, first = ga.arena, ga.flat, ga.first
-        luts = _luts(ctx.fwd_lut, ctx.table_lut, ctx.x.data_ptr(), d_out.data_ptr(),
-                     bwd=boffs.astype(np.uint64) + np.uint64(gbase), par=ga.lut)
-        hook = prog.overlap
-        if ctx.sy is not None:
-            ctx.sy.arenas = [ctx.arena, garena, parena]
-            _run_synced(_n.hip(), c.bwd.instantiate(Mvec, luts), dev, ctx.sy)
-        elif hook is not None and hook.ready() and len(poffs) > 1:
-            # all-reduce of the first part of the gradient buffer starts while the rest of the pass still runs
-            starts = np.append(poffs, ptotal)
-            want = ptotal // 2
-            op_i = int(np.searchsorted(starts[c.bwd_grads_done], want))          # first op with >= half final
-            op_i = min(op_i, len(c.bwd_grads_done) - 2)
-            split = int(starts[c.bwd_grads_done[op_i]]) // 4
-            _run(_n.hip(), c.bwd.instantiate(Mvec, luts), dev, mark_op=op_i, waiter=hook.comm_stream_ptr())
-            hook.early(pflat[first:first + split], first + split)
-        else:
-            _run(_n.hip(), c.bwd.instantiate(Mvec, luts), dev)
+        garena, gbase, boffs, ga = _issue_backward(prog, c, Mvec, ctx.fwd_lut, ctx.table_lut, ctx.x.data_ptr(),
+                                                   d_out.data_ptr(), d_out.device, ctx.sy, (ctx.arena,), prog.overlap)
         prog.account(c.acc_b, Mvec, ctx.tensors)
-        for p, v in zip(ga.params, ga.views):
-            p.grad = v if p.grad is None else p.grad + v
-        # data-parallel hook: the gradients of ``flat_params`` are views of ``flat_grad`` (parallel.GradSync)
-        prog.flat_grad, prog.flat_params, prog.flat_tail = pflat, ga.params, ga.tail
+        _store_grads(prog, ga)
         dx = _view(garena, gbase, boffs[c.dx_id], tuple(ctx.x.shape)) if c.dx_id >= 0 else None
         sp_ops.verify_pending_counts()       # (see forward: the counts of this pass's rulebooks, long written by now)
         return dx, None, None
@@ -934,14 +931,9 @@ class UNetLpTrainFunction(Function):
         need_dx = bool(x.requires_grad)
         x32 = x.detach().to(dtype).float().contiguous()      # what the walk's input convolution reads
         c = prog.compiled_lp_train(dtype, out_dtype == torch.float32, need_dx)
-        for bn in c.count:
-            wsis_ops._defer_batch_count(bn)
         Mvec = prog.Mvec
-        offs, total = c.fwd_arena.layout(Mvec)
-        arena, base = _arena_tensor(total, x.device)
         out = torch.empty((int(Mvec[0]), c.out_channels), dtype=out_dtype, device=x.device)
-        fwd_lut = offs.astype(np.uint64) + np.uint64(base)
-        _run(_n.hip(), c.fwd.instantiate(Mvec, _luts(fwd_lut, prog.table_lut, x32.data_ptr(), out.data_ptr())), x.device)
+        arena, _, _, fwd_lut = _issue_forward(prog, c, x32.data_ptr(), out.data_ptr(), x.device)
         if not (torch.is_grad_enabled() and (need_dx or anchor is not None)):
             sp_ops.verify_pending_counts()      # (see UNetFunction.forward)
         ctx.prog, ctx.c, ctx.arena, ctx.fwd_lut, ctx.x32, ctx.dtype, ctx.in_dtype = prog, c, arena, fwd_lut, x32, dtype, x.dtype
@@ -952,17 +944,10 @@ class UNetLpTrainFunction(Function):
     def backward(ctx, d_out):
         prog, c, Mvec = ctx.prog, ctx.c, ctx.Mvec
         d16 = sp_ops._aligned(d_out.to(ctx.dtype))      # the incoming gradient, cast once
-        dev = d16.device
-        boffs, btotal = c.bwd_arena.layout(Mvec)
-        poffs, ptotal = c.par_arena.layout(Mvec)
-        garena, gbase = _arena_tensor(btotal, dev)
-        ga = _GradArena.of_pass(prog, c, poffs, ptotal, dev)
-        luts = _luts(ctx.fwd_lut, ctx.table_lut, ctx.x32.data_ptr(), d16.data_ptr(),
-                     bwd=boffs.astype(np.uint64) + np.uint64(gbase), par=ga.lut)
-        _run(_n.hip(), c.bwd.instantiate(Mvec, luts), dev)
-        for p, v in zip(ga.params, ga.views):
-            p.grad = v if p.grad is None else p.grad + v
-        prog.flat_grad, prog.flat_params, prog.flat_tail = ga.flat, ga.params, ga.tail
+        # (overlap=None: the early all-reduce milestone is not used by this pass)
+        garena, gbase, boffs, ga = _issue_backward(prog, c, Mvec, ctx.fwd_lut, ctx.table_lut, ctx.x32.data_ptr(),
+                                                   d16.data_ptr(), d16.device)
+        _store_grads(prog, ga)
         dx = None
         if c.dx_id >= 0:
             dx = _view(garena, gbase, boffs[c.dx_id], (int(Mvec[0]), c.in_channels)).to(ctx.in_dtype)
@@ -1179,10 +1164,7 @@ def lp_pass_wanted(env, compute_dtype, grad_enabled, params_fp32, bn_eval, in_do
     UNet in evaluation mode with running statistics (``lp_bn_eval``), ``in_domain``: every product inside
     spconv.ops.lp_supported (``lp_in_domain``).  The cheap conditions come first: a callable runs only when everything
     in front of it holds.  Pure: no device."""
-    if not (env.get("WSIS_NATIVE_LP", "0") == "1" and env.get("WSIS_NATIVE_UNET", "1") != "0"
-            and compute_dtype in (torch.bfloat16, torch.float16) and not grad_enabled):
-        return False
-    return all(bool(c() if callable(c) else c) for c in (params_fp32, bn_eval, in_domain))
+    return _lp_wanted(env, "WSIS_NATIVE_LP", compute_dtype, grad_enabled, False, (params_fp32, bn_eval, in_domain))
 
 
 def lp_train_pass_wanted(env, compute_dtype, grad_enabled, params_fp32, bn_train, in_domain, synced):
@@ -1193,16 +1175,41 @@ def lp_train_pass_wanted(env, compute_dtype, grad_enabled, params_fp32, bn_train
     training mode with running statistics (``lp_bn_train``), ``in_domain``: every forward, dIn and dW product inside
     spconv.ops.lp_supported (``lp_train_in_domain``).  The cheap conditions come first: a callable runs only when
     everything in front of it holds.  Pure: no device."""
-    if not (env.get("WSIS_NATIVE_LP_TRAIN", "0") == "1" and env.get("WSIS_NATIVE_UNET", "1") != "0"
-            and compute_dtype in (torch.bfloat16, torch.float16) and grad_enabled):
+    return _lp_wanted(env, "WSIS_NATIVE_LP_TRAIN", compute_dtype, grad_enabled, True,
+                      (lambda: not _holds(synced), params_fp32, bn_train, in_domain))
+
+
+def _holds(check):
+    return bool(check() if callable(check) else check)
+
+
+def _lp_wanted(env, switch, compute_dtype, grad_enabled, want_grad, checks):
+    """the one dispatch rule of the 16-bit native passes: ``switch`` is on and WSIS_NATIVE_UNET not off, 16-bit compute
+    dtype, ``grad_enabled`` as the pass wants it, then ``checks`` in order, each run only if all before it hold"""
+    if not (env.get(switch, "0") == "1" and env.get("WSIS_NATIVE_UNET", "1") != "0"
+            and compute_dtype in (torch.bfloat16, torch.float16) and bool(grad_enabled) == want_grad):
         return False
-    if bool(synced() if callable(synced) else synced):
-        return False
-    return all(bool(c() if callable(c) else c) for c in (params_fp32, bn_train, in_domain))
+    return all(_holds(c) for c in checks)
 
 
 def _lp_modules(net):
     return [m for mod in (net.unet, net.output_layer) for m in mod.modules()]
+
+
+def _lp_bns(net, training):
+    """the BatchNorm layers of unet + output_layer if every one is in the mode ``training`` and keeps running statistics,
+    else None"""
+    bns = [m for m in _lp_modules(net) if isinstance(m, nn.BatchNorm1d)]
+    ok = all(m.training == training and m.track_running_stats and m.running_mean is not None and m.running_var is not None
+             for m in bns)
+    return bns if ok else None
+
+
+def _lp_convs(net):
+    """(K, Cin, Cout) of every sparse convolution of the UNet"""
+    import spconv
+    return [(int(np.prod(m.kernel_size)), m.in_channels, m.out_channels)
+            for m in net.unet.modules() if isinstance(m, spconv.conv.SparseConvolution)]
 
 
 def lp_params_fp32(net, device):
@@ -1217,34 +1224,27 @@ def lp_params_fp32(net, device):
 
 def lp_bn_eval(net):
     """every BatchNorm layer of unet + output_layer normalises with its running statistics"""
-    return all(not m.training and m.track_running_stats and m.running_mean is not None and m.running_var is not None
-               for m in _lp_modules(net) if isinstance(m, nn.BatchNorm1d))
+    return _lp_bns(net, False) is not None
 
 
 def lp_bn_train(net):
     """every BatchNorm layer of unet + output_layer takes batch statistics and updates running ones (channel counts
     inside the 16-bit BatchNorm kernels' domain)"""
-    return all(m.training and m.track_running_stats and m.running_mean is not None and m.running_var is not None
-               and m.momentum is not None and m.num_features % 8 == 0 and m.num_features <= 1024
-               for m in _lp_modules(net) if isinstance(m, nn.BatchNorm1d))
+    bns = _lp_bns(net, True)
+    return bns is not None and all(m.momentum is not None and m.num_features % 8 == 0 and m.num_features <= 1024 for m in bns)
 
 
 def lp_train_in_domain(net, rows):
     """every sparse product of a training pass of the UNet inside spconv.ops.lp_supported: forward, dIn (the channel
     counts swap) and dW (its dY below 2 GiB too); ``rows``: the finest level's row count, an upper bound of every level's"""
-    import spconv
     return all(sp_ops.lp_supported(K, Cin, Cout, rows) and sp_ops.lp_supported(K, Cout, Cin, rows)
-               and rows * Cout * 2 < (1 << 31)
-               for K, Cin, Cout in ((int(np.prod(m.kernel_size)), m.in_channels, m.out_channels)
-                                    for m in net.unet.modules() if isinstance(m, spconv.conv.SparseConvolution)))
+               and rows * Cout * 2 < (1 << 31) for K, Cin, Cout in _lp_convs(net))
 
 
 def lp_in_domain(net, rows):
     """every sparse product of the UNet (forward) inside spconv.ops.lp_supported; ``rows``: the finest level's row count,
     an upper bound of every level's"""
-    import spconv
-    return all(sp_ops.lp_supported(int(np.prod(m.kernel_size)), m.in_channels, m.out_channels, rows)
-               for m in net.unet.modules() if isinstance(m, spconv.conv.SparseConvolution))
+    return all(sp_ops.lp_supported(K, Cin, Cout, rows) for K, Cin, Cout in _lp_convs(net))
 
 
 def lp_out_dtype(compute_dtype, autocast):
@@ -1281,12 +1281,8 @@ def run_unet_lp(net, input_tensor, dtype, out_dtype):
     _n.require_cuda(x)
     x = x.detach().to(dtype).float().contiguous()
     c = prog.compiled_lp(dtype, out_dtype == torch.float32)
-    Mvec = prog.Mvec
-    offs, total = c.fwd_arena.layout(Mvec)
-    arena, base = _arena_tensor(total, x.device)
-    out = torch.empty((int(Mvec[0]), c.out_channels), dtype=out_dtype, device=x.device)
-    luts = _luts(offs.astype(np.uint64) + np.uint64(base), prog.table_lut, x.data_ptr(), out.data_ptr())
-    _run(_n.hip(), c.fwd.instantiate(Mvec, luts), x.device)
+    out = torch.empty((int(prog.Mvec[0]), c.out_channels), dtype=out_dtype, device=x.device)
+    _issue_forward(prog, c, x.data_ptr(), out.data_ptr(), x.device)      # (the arena is free once the call is issued)
     sp_ops.verify_pending_counts()
     return out
 

@@ -1,8 +1,10 @@
 """unet_program_golden.npz: what ``model/unet_native.py`` records for the sparse UNet, as the executor would receive it.
 
-``UNetProgram.compiled`` / ``.compiled_lp`` turn the module tree into ``wsis_op`` templates; nothing of that needs a
-device.  For every case of ``CASES`` this file instantiates the templates with a fixed pyramid (``MVEC``) and fake
-look-up tables and keeps
+``UNetProgram.compiled`` / ``.compiled_lp`` / ``.compiled_lp_train`` turn the module tree into ``wsis_op`` templates;
+nothing of that needs a device.  The case kinds are ``"fp32"`` (training and evaluation programs), ``"lp"`` (the 16-bit
+evaluation forward) and ``"lp_train"`` (the 16-bit training forward + backward, one case with a BatchNorm layer in
+evaluation mode).  For every case of ``CASES`` this file instantiates the templates with a fixed pyramid (``MVEC``) and
+fake look-up tables and keeps
 
   fwd, bwd                 the instantiated op arrays as raw bytes (every field of every op)
   *_offs, *_total          the three arena layouts
@@ -16,13 +18,13 @@ pointer of an op must point into exactly one parameter or buffer of the model an
 ``PARAM_TAG | index in sorted-name order << 32 | byte offset`` (fused statistics point into the middle of running_mean /
 running_var), so the arrays do not depend on where the process allocated the model.
 
-Only the surface of the recorder that its callers use is touched (``compiled``, ``compiled_lp``, ``instantiate``,
-``layout`` and the attributes of a compiled program), so the file can be run against any revision of
+Only the surface of the recorder that its callers use is touched (``compiled``, ``compiled_lp``, ``compiled_lp_train``,
+``instantiate``, ``layout`` and the attributes of a compiled program), so the file can be run against any revision of
 ``unet_native.py``: tests/test_unet_program_host.py pins later revisions to what the fixture's revision recorded.
 
     WSIS_EXPERIMENTAL=1 python __graft_entry__.py && python tests/golden/make_unet_program_golden.py
 
-(the EXPERIMENTAL build records all 15 cases; rebuild the default flavour afterwards)
+(the EXPERIMENTAL build records all 20 cases; rebuild the default flavour afterwards)
 """
 import contextlib
 import importlib
@@ -61,6 +63,11 @@ CASES["train_stat_fin"] = ("fp32", _T, {"WSIS_FUSE_BN_FIN": "1"}, True)
 CASES["train_bn_in"] = ("fp32", _T, {"WSIS_FUSE_BN_APPLY": "0"}, True)
 CASES["train_bn_in_lvl3_stat_fin_lvl3"] = ("fp32", _T, {"WSIS_FUSE_BN_APPLY": "3", "WSIS_FUSE_BN_FIN": "1",
                                                      "WSIS_FUSE_BN_FIN_LVL": "3"}, True)
+for _dt, _f32, _dx in (("bf16", False, False), ("bf16", True, True), ("fp16", False, True), ("fp16", True, False)):
+    CASES["lp_train_%s_f32out%d_dx%d" % (_dt, _f32, _dx)] = ("lp_train", dict(dtype=_dt, out_f32=_f32, need_dx=_dx), {}, False)
+# (the mixed-mode program: the named BatchNorm layer in evaluation mode inside a training pass)
+CASES["lp_train_bf16_one_bn_eval"] = ("lp_train", dict(dtype="bf16", out_f32=False, need_dx=True,
+                                                       bn_eval="unet.blocks.block0.conv_branch.0"), {}, False)
 
 
 def build_model():
@@ -138,11 +145,18 @@ def record(model, name):
     Mvec = np.asarray(MVEC, dtype=np.int64)
     out = {}
     with _environment(env):
-        model.train(bool(args.get("train", False)))
+        model.train(bool(args.get("train", kind == "lp_train")))
         prog = un.UNetProgram(model)
+        dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.get("dtype"))
         if kind == "lp":
-            dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args["dtype"]]
             c = prog.compiled_lp(dtype, args["out_f32"])
+        elif kind == "lp_train":
+            if args.get("bn_eval") is not None:
+                model.get_submodule(args["bn_eval"]).eval()
+            try:
+                c = prog.compiled_lp_train(dtype, args["out_f32"], args["need_dx"])
+            finally:
+                model.train()                    # (later cases must not see the layer in evaluation mode)
         else:
             if args.get("bn_sync"):
                 prog.bn_sync = object()          # compile only: any non-None object selects the synced recording

@@ -16,7 +16,9 @@ import wsis_native
 from tests.golden import make_executor_layout_golden as gen
 from tests.golden import make_unet_program_golden as prog
 
-CASES = sorted(prog.CASES)
+# (the 15 programs whose sizes executor_layout_golden.json recorded at its revision: the 16-bit training programs were
+# added to unet_program_golden.npz later)
+CASES = sorted(n for n, spec in prog.CASES.items() if spec[0] != "lp_train")
 ALIGN = 256
 N_REGIONS = 5      # 16-bit weights | transposed fp32 weights | weight-gradient slabs | resident deep-level run | per-op
 

@@ -1,6 +1,7 @@
 """CPU: the op lists, arena layouts and bookkeeping that model/unet_native.py records for the sparse UNet are byte for byte
 what tests/golden/unet_program_golden.npz holds (tests/golden/make_unet_program_golden.py: fp32 training and evaluation
-programs under every compile-time switch, the synced-BatchNorm recording, the 16-bit inference programs).  The recorder
+programs under every compile-time switch, the synced-BatchNorm recording, the 16-bit inference programs, the 16-bit
+training programs of kind ``"lp_train"``, one of them with a BatchNorm layer in evaluation mode).  The recorder
 needs no device; what it hands the executor is a byte array, so a change of the recorder that is meant to leave the
 passes alone is checked here, without a GPU."""
 import os
@@ -25,7 +26,7 @@ def model():
 
 
 def test_fixture_holds_every_case_and_nothing_else(golden):
-    assert len(gen.CASES) == 15
+    assert len(gen.CASES) == 20
     assert set(golden) == set(gen.CASES)
     assert os.path.getsize(gen.FIXTURE) < 100 * 1024
 
