@@ -5,6 +5,8 @@
 // the CUs, 1.3 TB/s, 233 us); here a workgroup takes 1,024 elements, every tensor in the same launch.
 #include "common.h"
 
+#include <cstddef>
+
 namespace wsis {
 namespace {
 
@@ -84,6 +86,141 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamSeg* __restrict__ 
   }
 }
 
+// ---- dynamic loss scaling for fp16 training (torch.amp.GradScaler: unscale_ + found_inf.item() + step + update, a dozen
+// foreach launches and one device->host read per step) in three launches without a read-back.  The state -- scale, overflow
+// flag, skip counters -- lives on the device; the host never learns whether a step was skipped.
+
+// the segment as wsis_adamw_step_scaled reads it: the slot of (step_size, inv_sqrt_bc2) carries the HOST's update count
+struct AdamSegScaled {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  int64_t n;
+  int64_t t_host;       // updates of this parameter the host has issued, this one included (skipped ones too)
+  float g_clamp;
+  float pad_;
+};
+static_assert(sizeof(AdamSegScaled) == sizeof(AdamSeg) && offsetof(AdamSegScaled, t_host) == offsetof(AdamSeg, step_size) &&
+                  offsetof(AdamSegScaled, g_clamp) == offsetof(AdamSeg, g_clamp) && offsetof(AdamSegScaled, n) == offsetof(AdamSeg, n),
+              "one table layout for the three entry points");
+
+// inf or NaN: all exponent bits set.  On the bits, so that no floating-point flag can fold the test away.
+__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// Reads g only (4 bytes per parameter).  A wave that saw a non-finite element stores 1.0f from one lane: every writer
+// stores the same value, nobody reads the flag in this launch, and nothing here ever stores 0.
+__global__ __launch_bounds__(256) void grad_nonfinite_kernel(const AdamSeg* __restrict__ segs,
+                                                             const int32_t* __restrict__ blocks,
+                                                             float* __restrict__ found_inf) {
+  const int s = blocks[2 * blockIdx.x], chunk = blocks[2 * blockIdx.x + 1];
+  const float* const g = segs[s].g;
+  const int64_t n = segs[s].n;
+  const int64_t i0 = (int64_t)chunk * AD_CHUNK + (int64_t)threadIdx.x * 4;
+  bool bad = false;
+  if (i0 < n) {
+    if (i0 + 4 <= n && (reinterpret_cast<uintptr_t>(g + i0) & 15) == 0) {
+      const float4 x = *reinterpret_cast<const float4*>(g + i0);
+      bad = ((int)nonfinite(x.x) | (int)nonfinite(x.y) | (int)nonfinite(x.z) | (int)nonfinite(x.w)) != 0;
+    } else {
+      for (int64_t i = i0; i < i0 + 4 && i < n; ++i) bad = bad || nonfinite(g[i]);
+    }
+  }
+  const unsigned long long m = __ballot(bad);
+  if (m != 0ull && (threadIdx.x & 63) == 0) *found_inf = 1.0f;
+}
+
+// The skip counters are race-free by construction: skipped[s] is WRITTEN only in a launch whose flag is set, by one thread
+// (thread 0 of chunk 0 of segment s), and in such a launch every other thread returns before it would read a counter; it
+// is READ only in a launch whose flag is clear, in which nobody writes it.  The flag itself is read-only here.
+__global__ __launch_bounds__(256) void adamw_scaled_kernel(const AdamSegScaled* __restrict__ segs,
+                                                           const int32_t* __restrict__ blocks, float decay, float omb1,
+                                                           float b2, float eps, float omb2, double lr, double beta1,
+                                                           double beta2, const float* __restrict__ grad_scale,
+                                                           const float* __restrict__ found_inf,
+                                                           int32_t* __restrict__ skipped) {
+  __shared__ float corr[3];
+  const int s = blocks[2 * blockIdx.x], chunk = blocks[2 * blockIdx.x + 1];
+  const AdamSegScaled sg = segs[s];
+  if (found_inf && *found_inf != 0.0f) {       // uniform over the launch: nothing of p, m, v or g is written
+    if (chunk == 0 && threadIdx.x == 0 && sg.n > 0) skipped[s] += 1;
+    return;
+  }
+  if (threadIdx.x == 0) {
+    // updates that took effect; both corrections in double and rounded once, as FlatAdamW.step does on the host
+    int64_t t = sg.t_host - (int64_t)skipped[s];
+    if (t < 1) t = 1;
+    corr[0] = (float)(lr / (1.0 - pow(beta1, (double)t)));
+    corr[1] = (float)(1.0 / sqrt(1.0 - pow(beta2, (double)t)));
+    corr[2] = grad_scale ? (float)(1.0 / (double)*grad_scale) : 1.0f;      // torch's unscale_ rounding
+  }
+  __syncthreads();
+  const float step_size = corr[0], inv_sqrt_bc2 = corr[1], inv = corr[2];
+  const float gc = sg.g_clamp;
+  float* const gw = const_cast<float*>(sg.g);
+  const int64_t i0 = (int64_t)chunk * AD_CHUNK + (int64_t)threadIdx.x * 4;
+  if (i0 >= sg.n) return;
+  const bool vec = i0 + 4 <= sg.n && ((reinterpret_cast<uintptr_t>(sg.p + i0) | reinterpret_cast<uintptr_t>(sg.g + i0) |
+                                       reinterpret_cast<uintptr_t>(sg.m + i0) | reinterpret_cast<uintptr_t>(sg.v + i0)) & 15) == 0;
+  if (vec) {
+    float4 p = *reinterpret_cast<float4*>(sg.p + i0);
+    float4 g = *reinterpret_cast<const float4*>(sg.g + i0);
+    g.x *= inv;
+    g.y *= inv;
+    g.z *= inv;
+    g.w *= inv;
+    if (gc > 0.0f) {                           // the clamp acts on the UNSCALED gradient, which is what .grad then holds
+      g.x = clamp_keep_nan(g.x, gc);
+      g.y = clamp_keep_nan(g.y, gc);
+      g.z = clamp_keep_nan(g.z, gc);
+      g.w = clamp_keep_nan(g.w, gc);
+      *reinterpret_cast<float4*>(gw + i0) = g;
+    }
+    float4 m = *reinterpret_cast<float4*>(sg.m + i0);
+    float4 v = *reinterpret_cast<float4*>(sg.v + i0);
+    adam_one(p.x, g.x, m.x, v.x, decay, omb1, b2, eps, omb2, step_size, inv_sqrt_bc2);
+    adam_one(p.y, g.y, m.y, v.y, decay, omb1, b2, eps, omb2, step_size, inv_sqrt_bc2);
+    adam_one(p.z, g.z, m.z, v.z, decay, omb1, b2, eps, omb2, step_size, inv_sqrt_bc2);
+    adam_one(p.w, g.w, m.w, v.w, decay, omb1, b2, eps, omb2, step_size, inv_sqrt_bc2);
+    *reinterpret_cast<float4*>(sg.p + i0) = p;
+    *reinterpret_cast<float4*>(sg.m + i0) = m;
+    *reinterpret_cast<float4*>(sg.v + i0) = v;
+  } else {
+    for (int64_t i = i0; i < i0 + 4 && i < sg.n; ++i) {
+      float p = sg.p[i], m = sg.m[i], v = sg.v[i];
+      float g = sg.g[i] * inv;
+      if (gc > 0.0f) {
+        g = clamp_keep_nan(g, gc);
+        gw[i] = g;
+      }
+      adam_one(p, g, m, v, decay, omb1, b2, eps, omb2, step_size, inv_sqrt_bc2);
+      sg.p[i] = p;
+      sg.m[i] = m;
+      sg.v[i] = v;
+    }
+  }
+}
+
+// torch._amp_update_scale_ in one thread, then the flag is cleared for the next step
+__global__ void loss_scale_update_kernel(float* __restrict__ scale, int32_t* __restrict__ tracker,
+                                         float* __restrict__ found_inf, double growth, double backoff, int32_t interval) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  if (*found_inf != 0.0f) {
+    *scale = (float)((double)*scale * backoff);
+    *tracker = 0;
+  } else {
+    const int32_t ok = *tracker + 1;
+    if (ok == interval) {
+      const float grown = (float)((double)*scale * growth);
+      if (!nonfinite(grown)) *scale = grown;
+      *tracker = 0;
+    } else {
+      *tracker = ok;
+    }
+  }
+  *found_inf = 0.0f;
+}
+
 }  // namespace
 }  // namespace wsis
 
@@ -103,6 +240,44 @@ int wsis_adamw_step(const void* d_segments, const int32_t* d_blocks, int64_t n_b
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)n_blocks), dim3(256), 0, as_stream(stream),
                      static_cast<const AdamSeg*>(d_segments), d_blocks, (float)(1.0 - lr * weight_decay),
                      (float)(1.0 - beta1), (float)beta2, (float)eps, (float)(1.0 - beta2));
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+int wsis_grad_nonfinite(const void* d_segments, const int32_t* d_blocks, int64_t n_blocks, float* d_found_inf,
+                        void* stream) {
+  WSIS_REQUIRE(n_blocks >= 0, "bad args");
+  if (n_blocks == 0) return WSIS_OK;
+  WSIS_REQUIRE(d_segments && d_blocks && d_found_inf, "null pointer");
+  WSIS_REQUIRE(n_blocks < ((int64_t)1 << 31), "too many blocks");
+  hipLaunchKernelGGL(grad_nonfinite_kernel, dim3((unsigned)n_blocks), dim3(256), 0, as_stream(stream),
+                     static_cast<const AdamSeg*>(d_segments), d_blocks, d_found_inf);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+int wsis_adamw_step_scaled(const void* d_segments, const int32_t* d_blocks, int64_t n_blocks, double lr, double beta1,
+                           double beta2, double eps, double weight_decay, const float* d_grad_scale,
+                           const float* d_found_inf, int32_t* d_skipped, void* stream) {
+  WSIS_REQUIRE(n_blocks >= 0, "bad args");
+  if (n_blocks == 0) return WSIS_OK;
+  WSIS_REQUIRE(d_segments && d_blocks, "null pointer");
+  WSIS_REQUIRE(d_skipped, "null skip counters");
+  WSIS_REQUIRE(n_blocks < ((int64_t)1 << 31), "too many blocks");
+  hipLaunchKernelGGL(adamw_scaled_kernel, dim3((unsigned)n_blocks), dim3(256), 0, as_stream(stream),
+                     static_cast<const AdamSegScaled*>(d_segments), d_blocks, (float)(1.0 - lr * weight_decay),
+                     (float)(1.0 - beta1), (float)beta2, (float)eps, (float)(1.0 - beta2), lr, beta1, beta2, d_grad_scale,
+                     d_found_inf, d_skipped);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+int wsis_loss_scale_update(float* d_scale, int32_t* d_growth_tracker, float* d_found_inf, double growth_factor,
+                           double backoff_factor, int32_t growth_interval, void* stream) {
+  WSIS_REQUIRE(d_scale && d_growth_tracker && d_found_inf, "null pointer");
+  WSIS_REQUIRE(growth_interval >= 1, "bad args");
+  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(1), 0, as_stream(stream), d_scale, d_growth_tracker,
+                     d_found_inf, growth_factor, backoff_factor, growth_interval);
   WSIS_LAUNCH_CHECK();
   return WSIS_OK;
 }

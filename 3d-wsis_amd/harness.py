@@ -441,14 +441,16 @@ def forward_loss(model, criterion, batch, cfg, epoch=5):
     return loss, ret
 
 
-def train_step(model, criterion, optimizer, batch, cfg, epoch=5, grad_sync=None, pipeline=None):
+def train_step(model, criterion, optimizer, batch, cfg, epoch=5, grad_sync=None, pipeline=None, scaler=None):
     """one iteration of train_scannetv2.py:143-252 (forward, loss, backward, ECC grad clamp, AdamW step).
-    ``pipeline``: a started spconv.ops.RulebookPipeline of the NEXT batch, advanced between the phases."""
+    ``pipeline``: a started spconv.ops.RulebookPipeline of the NEXT batch, advanced between the phases.
+    ``scaler``: a wsis_optim.LossScaler (fp16 training): the loss is scaled before backward, the step checks and unscales
+    the (all-reduced) gradients on the device and skips itself on overflow, the ECC clamp acts on the unscaled values."""
     loss, ret = forward_loss(model, criterion, batch, cfg, epoch)
     if pipeline is not None:
         pipeline.pump()
     optimizer.zero_grad(set_to_none=True)
-    loss.backward()
+    (loss if scaler is None else scaler.scale(loss)).backward()
     if pipeline is not None:
         pipeline.pump()
     if grad_sync is not None:
@@ -464,7 +466,11 @@ def train_step(model, criterion, optimizer, batch, cfg, epoch=5, grad_sync=None,
         if grads:
             torch._foreach_clamp_min_(grads, -1.0)
             torch._foreach_clamp_max_(grads, 1.0)
-    optimizer.step()
+    if scaler is None:
+        optimizer.step()
+    else:
+        scaler.step(optimizer)
+        scaler.update()
     if pipeline is not None:
         pipeline.pump()
     return loss.detach(), ret

@@ -4,7 +4,12 @@
 Same update rule as ``torch.optim.AdamW`` (tested against it step by step); the moments live in two flat buffers, a
 small (pointer, size) table per step tells the kernel where each parameter, gradient and moment slice is.  The table
 goes through a ring of pinned host buffers: the copy of step t is still queued on the stream while the host already
-prepares step t+1 (gradient tensors of most parameters are new objects every backward pass)."""
+prepares step t+1 (gradient tensors of most parameters are new objects every backward pass).
+
+fp16 training: ``LossScaler`` is dynamic loss scaling with its state on the device -- the non-finite check
+(``wsis_grad_nonfinite``), the unscale, the skip decision and the step count (``wsis_adamw_step_scaled``) and the scale
+update (``wsis_loss_scale_update``) are three launches, and nothing is read back: the host never learns whether a step
+was skipped.  ``torch.amp.GradScaler`` drives ``FlatAdamW`` through torch's fused-optimizer protocol as well."""
 import numpy as np
 import torch
 
@@ -16,7 +21,15 @@ _RING = 4
 class FlatAdamW(torch.optim.Optimizer):
     """A ``torch.optim.Optimizer`` (one parameter group): ``param_groups[0]`` is live -- the step reads ``lr``,
     ``betas``, ``eps`` and ``weight_decay`` from it, so the reference's ``PolyLR`` (an ``_LRScheduler``, stepped per
-    epoch, ``utils/lr_scheduler.py``) and its ``save_checkpoint`` isinstance check work on it unchanged."""
+    epoch, ``utils/lr_scheduler.py``) and its ``save_checkpoint`` isinstance check work on it unchanged.
+
+    Loss scaling: the step honours torch's protocol attributes ``grad_scale`` and ``found_inf`` (fp32 one-element device
+    tensors; absent or None: scale 1 / never skipped), so ``torch.amp.GradScaler.step`` hands both over without reading
+    ``found_inf`` back.  A step the device skips writes nothing and counts itself per parameter on the device
+    (``_skipped``); ``steps`` keeps counting calls with a gradient.  A parameter without a gradient clamp keeps the SCALED
+    values in ``.grad`` after a scaled step (the step does not write its gradient back); a clamped one holds the clamped
+    unscaled values."""
+    _step_supports_amp_scaling = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         params = list(params)
@@ -64,6 +77,7 @@ class FlatAdamW(torch.optim.Optimizer):
         self._dev = [torch.empty((n, 7), dtype=torch.int64, device=dev) for _ in range(_RING)]
         self._done = [None] * _RING
         self._slot = 0
+        self._skipped = None        # int32 [n]: steps the device skipped, per parameter; made by the first scaled step
 
     # hyper-parameters live in param_groups[0] (schedulers write there); the attributes are views of it
     lr = property(lambda self: float(self.param_groups[0]["lr"]),
@@ -91,14 +105,10 @@ class FlatAdamW(torch.optim.Optimizer):
             elif p.grad is not None:
                 p.grad.zero_()
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        if len(self.param_groups) != 1:
-            raise ValueError("FlatAdamW takes ONE parameter group")
+    def _stage_table(self, scaled):
+        """fill the segment table of this step (the ONE place), queue its copy through the ring, return the device
+        table.  ``scaled``: slot 5 carries the host's update count (wsis_adamw_step_scaled forms the bias corrections
+        from it and the skip counters), else the two corrections as fp32."""
         tab = self._table
         grads = [p.grad for p in self.params]
         for i, g in enumerate(grads):                 # slow path only for a gradient the kernel cannot read as is
@@ -110,9 +120,12 @@ class FlatAdamW(torch.optim.Optimizer):
         live = g_ptr != 0
         tab[:, 4] = np.where(live, self._numel, 0)
         self.steps += live
-        t = np.maximum(self.steps, 1).astype(np.float64)
-        corr = np.stack([self.lr / (1.0 - self.betas[0] ** t), 1.0 / np.sqrt(1.0 - self.betas[1] ** t)], 1)
-        tab[:, 5] = np.ascontiguousarray(corr.astype(np.float32)).view(np.int64).reshape(-1)
+        if scaled:
+            tab[:, 5] = self.steps
+        else:
+            t = np.maximum(self.steps, 1).astype(np.float64)
+            corr = np.stack([self.lr / (1.0 - self.betas[0] ** t), 1.0 / np.sqrt(1.0 - self.betas[1] ** t)], 1)
+            tab[:, 5] = np.ascontiguousarray(corr.astype(np.float32)).view(np.int64).reshape(-1)
         k = self._slot
         self._slot = (k + 1) % _RING
         if self._done[k] is not None:
@@ -122,7 +135,38 @@ class FlatAdamW(torch.optim.Optimizer):
         ev = torch.cuda.Event()
         ev.record()
         self._done[k] = ev
-        _n.check(_n.hip().wsis_adamw_step(_n.ptr(self._dev[k]), _n.ptr(self._blocks), self._n_blocks, self.lr,
+        return self._dev[k]
+
+    def _step_scaled(self, grad_scale, found_inf, check):
+        """the step through wsis_adamw_step_scaled; ``check``: wsis_grad_nonfinite first, over the same table slot"""
+        for t in (grad_scale, found_inf):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
+                raise ValueError("grad_scale / found_inf: one-element fp32 tensors on the device")
+        if self._skipped is None:
+            self._skipped = torch.zeros(len(self.params), dtype=torch.int32, device=self.params[0].device)
+        lib, dev_tab, st = _n.hip(), self._stage_table(True), _n.stream_ptr()
+        if check:
+            _n.check(lib.wsis_grad_nonfinite(_n.ptr(dev_tab), _n.ptr(self._blocks), self._n_blocks, _n.ptr(found_inf), st),
+                     "grad_nonfinite")
+        _n.check(lib.wsis_adamw_step_scaled(_n.ptr(dev_tab), _n.ptr(self._blocks), self._n_blocks, self.lr, self.betas[0],
+                                            self.betas[1], self.eps, self.weight_decay, _n.ptr(grad_scale),
+                                            _n.ptr(found_inf), _n.ptr(self._skipped), st), "adamw_step_scaled")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if len(self.param_groups) != 1:
+            raise ValueError("FlatAdamW takes ONE parameter group")
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        if self._skipped is not None or grad_scale is not None or found_inf is not None:
+            # once a step may have been skipped on the device, only the device knows the update counts
+            self._step_scaled(grad_scale, found_inf, False)
+            return loss
+        dev_tab = self._stage_table(False)
+        _n.check(_n.hip().wsis_adamw_step(_n.ptr(dev_tab), _n.ptr(self._blocks), self._n_blocks, self.lr,
                                           self.betas[0], self.betas[1], self.eps, self.weight_decay,
                                           _n.stream_ptr()), "adamw_step")
         return loss
@@ -130,12 +174,15 @@ class FlatAdamW(torch.optim.Optimizer):
     # state in the layout of torch.optim.AdamW.state_dict()["state"] (checkpoint interchange)
     def state_dict(self):
         state, off = {}, 0
+        steps = self.steps          # updates that took effect: the one read-back of loss scaling, at checkpoint time
+        if self._skipped is not None:
+            steps = steps - self._skipped.cpu().numpy()
         for i, p in enumerate(self.params):
             n = p.numel()
-            if self.steps[i] == 0:
+            if steps[i] == 0:
                 off += (n + 3) // 4 * 4
                 continue                                  # torch creates the state at the first update
-            state[i] = {"step": torch.tensor(float(self.steps[i])),
+            state[i] = {"step": torch.tensor(float(steps[i])),
                         "exp_avg": self.exp_avg[off:off + n].view_as(p).clone(),
                         "exp_avg_sq": self.exp_avg_sq[off:off + n].view_as(p).clone()}
             off += (n + 3) // 4 * 4
@@ -145,6 +192,8 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def load_state_dict(self, sd):
         off = 0
+        if self._skipped is not None:
+            self._skipped.zero_()                         # the checkpoint's counts are the effective ones
         for i, p in enumerate(self.params):
             n = p.numel()
             st = sd["state"].get(i)
@@ -161,3 +210,77 @@ class FlatAdamW(torch.optim.Optimizer):
         for k, v in g.items():
             if k != "params":
                 self.param_groups[0][k] = tuple(v) if k == "betas" else v
+
+
+class LossScaler(object):
+    """Dynamic loss scaling for fp16 training: the subset of ``torch.amp.GradScaler`` the training loop uses, with the
+    scale, the growth tracker and the overflow flag in one small device block and no read-back in a step::
+
+        scaler.scale(loss).backward()      # one multiply by the device scale
+        scaler.step(optimizer)             # wsis_grad_nonfinite + wsis_adamw_step_scaled over one table slot
+        scaler.update()                    # wsis_loss_scale_update (one thread), clears the flag
+
+    An overflow step writes no parameter, moment or gradient byte and halves the scale; ``growth_interval`` clean steps
+    in a row double it (never to inf).  Several ranks: ``step`` runs after the gradient all-reduce, in which inf and NaN
+    survive the sum, so every rank sees the same flag and takes the same decision without another collective."""
+
+    def __init__(self, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, enabled=True,
+                 device=None):
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise _n.WsisError("LossScaler runs on the MI355X only (there is no CPU fallback)")
+        if growth_factor <= 1.0 or not 0.0 < backoff_factor < 1.0 or int(growth_interval) < 1:
+            raise ValueError("LossScaler: growth_factor > 1, 0 < backoff_factor < 1, growth_interval >= 1")
+        self.growth_factor, self.backoff_factor = float(growth_factor), float(backoff_factor)
+        self.growth_interval, self.enabled = int(growth_interval), bool(enabled)
+        self._block = torch.zeros(4, dtype=torch.float32, device=dev)       # scale, found_inf, tracker (int32), unused
+        self._block[0] = float(init_scale)
+        self._scale, self._found_inf = self._block[0:1], self._block[1:2]
+        self._tracker = self._block[2:3].view(torch.int32)
+        self._stepped = False
+
+    def scale(self, loss):
+        return loss * self._block[0] if self.enabled else loss
+
+    def step(self, optimizer):
+        if not isinstance(optimizer, FlatAdamW):
+            raise TypeError("LossScaler.step drives wsis_optim.FlatAdamW only (torch.amp.GradScaler takes any optimizer)")
+        if not self.enabled:
+            return optimizer.step()
+        if self._stepped:
+            raise RuntimeError("step() has already been called since the last update()")
+        if len(optimizer.param_groups) != 1:
+            raise ValueError("FlatAdamW takes ONE parameter group")
+        with torch.no_grad():
+            optimizer._step_scaled(self._scale, self._found_inf, True)
+        self._stepped = True
+
+    def update(self):
+        if not self.enabled:
+            return
+        _n.check(_n.hip().wsis_loss_scale_update(_n.ptr(self._scale), _n.ptr(self._tracker), _n.ptr(self._found_inf),
+                                                 self.growth_factor, self.backoff_factor, self.growth_interval,
+                                                 _n.stream_ptr()), "loss_scale_update")
+        self._stepped = False
+
+    def get_scale(self):
+        """the current scale -- a SYNCHRONISING read of the device (for logs, not for the step)"""
+        return float(self._block[0]) if self.enabled else 1.0
+
+    def state_dict(self):
+        """the layout of ``torch.amp.GradScaler.state_dict()`` (its ``_growth_tracker`` is ``growth_tracker`` here; a
+        checkpoint of either loads); reads the device"""
+        if not self.enabled:
+            return {}
+        return {"scale": float(self._block[0]), "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "growth_tracker": int(self._tracker[0])}
+
+    def load_state_dict(self, sd):
+        if not self.enabled:
+            return
+        self.growth_factor, self.backoff_factor = float(sd["growth_factor"]), float(sd["backoff_factor"])
+        self.growth_interval = int(sd["growth_interval"])
+        self._block[0] = float(sd["scale"])
+        self._tracker[0] = int(sd["growth_tracker"] if "growth_tracker" in sd else sd["_growth_tracker"])
+        self._found_inf.zero_()
+        self._stepped = False

@@ -1018,6 +1018,32 @@ int32_t wsis_adamw_chunk(void);
 int wsis_adamw_step(const void* d_segments, const int32_t* d_blocks, int64_t n_blocks, double lr, double beta1,
                     double beta2, double eps, double weight_decay, void* stream);
 
+/* ---- dynamic loss scaling for fp16 training, state on the device.  Replaces torch.amp.GradScaler around the step:
+ * unscale_ (a Python walk over every gradient and multi-tensor foreach launches), found_inf.item() (a device->host
+ * read on every step) and the host's decision whether optimizer.step() runs -- here three launches and no read-back.
+ * All three take the segment and block tables of the optimizer step above.
+ *
+ * grad_nonfinite: reads the gradients only; any +-inf or NaN element stores 1.0f to *d_found_inf.  Never stores 0.
+ *
+ * adamw_step_scaled: d_grad_scale, d_found_inf: fp32 [1] on the device, either may be NULL (scale 1 / never skipped);
+ * d_skipped: int32 [n_segments], zero-filled by the caller once.  *d_found_inf != 0: no parameter, moment or gradient
+ * byte is written and d_skipped[s] += 1 for every segment with n > 0.  Otherwise the gradient is g * inv with
+ * inv = (float)(1.0 / (double)scale) (torch's unscale_ rounding; exact for a power of two); a segment with g_clamp > 0
+ * clamps THAT value and writes it back, a segment without does not write its gradient: its .grad still holds the
+ * scaled values after the step.  For this entry point the 8 bytes of (step_size, inv_sqrt_bc2) hold int64 t_host, the
+ * updates the host has issued for the parameter (skipped ones included); the kernel forms t = t_host - d_skipped[s]
+ * and both corrections from lr, beta1, beta2 in double, rounded once.
+ *
+ * loss_scale_update: torch._amp_update_scale_ (overflow: scale *= backoff, tracker = 0; else tracker + 1 and at
+ * growth_interval scale *= growth if that is finite, tracker = 0), then *d_found_inf = 0 for the next step. */
+int wsis_grad_nonfinite(const void* d_segments, const int32_t* d_blocks, int64_t n_blocks, float* d_found_inf,
+                        void* stream);
+int wsis_adamw_step_scaled(const void* d_segments, const int32_t* d_blocks, int64_t n_blocks, double lr, double beta1,
+                           double beta2, double eps, double weight_decay, const float* d_grad_scale,
+                           const float* d_found_inf, int32_t* d_skipped, void* stream);
+int wsis_loss_scale_update(float* d_scale, int32_t* d_growth_tracker, float* d_found_inf, double growth_factor,
+                           double backoff_factor, int32_t growth_interval, void* stream);
+
 /* ---- op-list executor: one C call issues a recorded forward or backward pass of the sparse UNet ------------
  * Replaces the Python-dispatched module walk of sparse_unet3d.py:103-350 (ResidualBlock.forward / UBlock.forward
  * and their autograd backward): the host records the pass as wsis_op records (plain device pointers + sizes) and
