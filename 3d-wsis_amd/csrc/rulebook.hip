@@ -615,20 +615,33 @@ int down_keys_sorted(const int32_t* d_indices_in, int64_t M_in, const int32_t* h
   return WSIS_OK;
 }
 
+// The ONE rule that chooses the form of the output keys of a strided level (wsis_rulebook_down_form answers it to a
+// caller, down_keys_bitmap acts on it): bitmap when every input voxel has one output cell (k == s, p == 0), the batch
+// size is known, the output grid has 1 .. 2^31 cells and the bitmap with its chunk sums fits the level's workspace.
+struct BitmapPlan {
+  int64_t n_cells, n_words, n_chunks;
+};
+bool down_form_is_bitmap(int64_t M_in, const int32_t* h_out_shape3, const int32_t* k, const int32_t* s3, const int32_t* p,
+                         int32_t batch_size, int64_t ws_bytes, BitmapPlan& pl) {
+  for (int j = 0; j < 3; ++j)
+    if (k[j] != s3[j] || p[j] != 0 || k[j] < 1) return false;
+  if (batch_size < 1 || M_in < 1) return false;
+  pl.n_cells = (int64_t)batch_size * h_out_shape3[0] * h_out_shape3[1] * h_out_shape3[2];
+  if (pl.n_cells < 1 || pl.n_cells > ((int64_t)1 << 31)) return false;
+  pl.n_words = (pl.n_cells + 31) >> 5;
+  pl.n_chunks = (pl.n_words + BM_WORDS_PER_WG - 1) / BM_WORDS_PER_WG;
+  const int64_t need = (int64_t)align256((size_t)pl.n_words * 4) + (int64_t)align256((size_t)pl.n_chunks * 4);
+  return need <= ws_bytes && pl.n_chunks <= (1 << 22);
+}
+
 // bitmap form of wsis_rulebook_down_keys (see down_mark_kernel); false: does not apply, nothing was issued
 bool down_keys_bitmap(const int32_t* d_indices_in, int64_t M_in, const int32_t* h_in_shape3, const int32_t* h_out_shape3,
                       const int32_t* k, const int32_t* s3, const int32_t* p, int32_t batch_size, int64_t* d_out_keys,
                       int32_t* d_count, void* d_ws, int64_t ws_bytes, hipStream_t st, int* rc_out) {
   *rc_out = WSIS_OK;
-  for (int j = 0; j < 3; ++j)
-    if (k[j] != s3[j] || p[j] != 0) return false;
-  if (batch_size < 1 || M_in < 1 || !d_ws) return false;
-  const int64_t n_cells = (int64_t)batch_size * h_out_shape3[0] * h_out_shape3[1] * h_out_shape3[2];
-  if (n_cells < 1 || n_cells > ((int64_t)1 << 31)) return false;
-  const int64_t n_words = (n_cells + 31) >> 5;
-  const int64_t n_chunks = (n_words + BM_WORDS_PER_WG - 1) / BM_WORDS_PER_WG;
-  const int64_t need = (int64_t)align256((size_t)n_words * 4) + (int64_t)align256((size_t)n_chunks * 4);
-  if (need > ws_bytes || n_chunks > (1 << 22)) return false;
+  BitmapPlan pl;
+  if (!d_ws || !down_form_is_bitmap(M_in, h_out_shape3, k, s3, p, batch_size, ws_bytes, pl)) return false;
+  const int64_t n_cells = pl.n_cells, n_words = pl.n_words, n_chunks = pl.n_chunks;
   Geo g;
   if (fill_geo(g, h_in_shape3, h_out_shape3, k, s3, p) != 0) return false;
   uint32_t* bitmap = static_cast<uint32_t*>(d_ws);
@@ -794,6 +807,16 @@ int64_t wsis_rulebook_down_workspace_bytes(int64_t n_cand) {
   // layout: [sorted keys n_cand*8][temp max(sort,unique)]
   return (int64_t)(align256((size_t)n_cand * 8) + align256(sort_bytes > uniq_bytes ? sort_bytes : uniq_bytes) +
                    256);
+}
+
+int32_t wsis_rulebook_down_form(int64_t M_in, const int32_t* h_out_shape3, const int32_t* h_ksize3,
+                                const int32_t* h_stride3, const int32_t* h_pad3, int32_t batch_size) {
+  if (!h_out_shape3 || !h_ksize3 || !h_stride3 || !h_pad3 || M_in < 0) return -1;
+  // the workspace of the level is what wsis_rulebook_pyramid hands the build: sized for the sort form of its candidates
+  const int64_t ws_bytes = wsis_rulebook_down_workspace_bytes(wsis_rulebook_down_ncand(M_in, h_ksize3, h_stride3, h_pad3));
+  if (ws_bytes < 0) return -1;
+  BitmapPlan pl;
+  return down_form_is_bitmap(M_in, h_out_shape3, h_ksize3, h_stride3, h_pad3, batch_size, ws_bytes, pl) ? 1 : 0;
 }
 
 int wsis_rulebook_down_keys(const int32_t* d_indices_in, int64_t M_in, const int32_t* h_in_shape3,

@@ -101,6 +101,7 @@ _HIP_SIGS = {
     "wsis_spconv_dw_bn": (I32, [P, P, P, P, P, F32, I32, P, P, I32, P, P, I64, I64, I32, I32, I32, P, I64, P]),
     "wsis_rulebook_pyramid_layout": (I64, [I64, P, I32, P]),
     "wsis_rulebook_pyramid": (I32, [P, I64, P, P, I32, I32, I32, P, I64, P]),
+    "wsis_rulebook_down_form": (I32, [I64, P, P, P, P, I32]),
     "wsis_rulebook_pack": (I32, [P, P, P, I64, I32, P]),
     "wsis_rulebook_pack_batch": (I32, [I32, P, P, P, P, P, P]),
     "wsis_prof_enable": (I32, [I32]),

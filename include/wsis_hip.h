@@ -196,6 +196,13 @@ int64_t wsis_rulebook_pyramid_layout(int64_t M0, const int64_t* h_counts, int32_
 int wsis_rulebook_pyramid(const int32_t* d_indices0, int64_t M0, const int32_t* h_shape3, const int64_t* h_counts,
                           int32_t n_levels, int32_t batch_size, int32_t block_shift, void* d_arena, int64_t arena_bytes,
                           void* stream);
+/* Which form the output coordinates of a strided level take inside wsis_rulebook_pyramid (a query: nothing is issued):
+ * 1 = bitmap over the output grid + prefix popcount (k == s, p == 0, batch_size >= 1, 1 <= batch_size * out cells
+ * <= 2^31, and the bitmap with its chunk sums fits wsis_rulebook_down_workspace_bytes of the level's candidates),
+ * 0 = candidate keys + sort + unique, -1 = bad arguments.  The build itself decides by the same function; both forms
+ * give the same rows (ascending linear index; batch indices outside [0, batch_size) are not part of the build). */
+int32_t wsis_rulebook_down_form(int64_t M_in, const int32_t* h_out_shape3, const int32_t* h_ksize3,
+                                const int32_t* h_stride3, const int32_t* h_pad3, int32_t batch_size);
 
 /* ---- a7-a11: sparse convolution [UPSTREAM spconv indiceConv / indiceConvBackward] -----------
  * out[r,:] = sum_k X[nbr[k][r],:] @ W[k]  (rows with nbr<0 contribute nothing), fp32.
