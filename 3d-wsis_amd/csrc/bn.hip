@@ -11,8 +11,9 @@
 // bn_chunk_walk / bn_lane_fold / bn_ticket_sum); every launch form -- stand-alone two-launch and one-launch, two-level
 // from centred partials, small finish + apply, polled finish + apply (EXPERIMENTAL) -- is a walk around those, so the
 // forms agree bit for bit by construction.  The stand-alone reductions and the backward apply are templates on the element
-// type: the 16-bit entry points (wsis_bn_stats_lp, wsis_bn_bwd_lp, wsis_bn_apply_lp) are the fp32 kernels reading bf16 /
-// fp16 rows widened exactly, with the fp32 forms' launch plans (bn_stats_run, bn_bwd_reduce_run).
+// type: the 16-bit entry points (wsis_bn_stats_lp, wsis_bn_bwd_lp, wsis_bn_bwd_apply_lp, wsis_bn_apply_lp) are the fp32
+// kernels reading bf16 / fp16 rows widened exactly, with the fp32 forms' launch plans (bn_stats_run, bn_bwd_reduce_run).
+// The wsis_bn_sync_* helpers of a layer whose statistics are shared across ranks stand at the end of the namespace.
 #include <cstdlib>
 #include <initializer_list>
 
@@ -1143,20 +1144,30 @@ static int bn_bwd_reduce_run(const T* d_x, const T* d_dy, const float* d_mean, c
   }
   return WSIS_OK;
 }
-// reduction, then dx (d_dx == nullptr: none) as TO = T, or as float when out_fp32
+// the apply pass of a 16-bit backward (wsis_bn_bwd_lp, wsis_bn_bwd_apply_lp): dx as TO = T, or as float when out_fp32
 template <typename T>
-static int bn_bwd_lp_run(const void* d_x, const void* d_dy, const float* d_mean, const float* d_var, const float* d_gamma,
-                         const float* d_beta, float eps, int relu, int training, void* d_dx, int out_fp32,
-                         float* d_dgamma, float* d_dbeta, const void* d_addend, int64_t M, int C, void* d_ws,
-                         hipStream_t st) {
+static int bn_bwd_apply_lp_run(const void* d_x, const void* d_dy, const float* d_mean, const float* d_var,
+                               const float* d_gamma, const float* d_beta, const float* d_dgamma, const float* d_dbeta,
+                               const void* d_addend, float eps, int relu, int training, void* d_dx, int out_fp32, int64_t M,
+                               int C, hipStream_t st) {
   const T *x = static_cast<const T*>(d_x), *dy = static_cast<const T*>(d_dy), *ad = static_cast<const T*>(d_addend);
-  const int rc = bn_bwd_reduce_run(x, dy, d_mean, d_var, d_gamma, d_beta, eps, relu, d_dgamma, d_dbeta, M, C, d_ws, st);
-  if (rc != WSIS_OK || !d_dx) return rc;
   if (out_fp32)
     return launch_bn_bwd_apply(x, dy, d_mean, d_var, d_gamma, d_beta, d_dgamma, d_dbeta, ad, eps, relu, training,
                                static_cast<float*>(d_dx), M, C, st);
   return launch_bn_bwd_apply(x, dy, d_mean, d_var, d_gamma, d_beta, d_dgamma, d_dbeta, ad, eps, relu, training,
                              static_cast<T*>(d_dx), M, C, st);
+}
+// reduction, then dx (d_dx == nullptr: none)
+template <typename T>
+static int bn_bwd_lp_run(const void* d_x, const void* d_dy, const float* d_mean, const float* d_var, const float* d_gamma,
+                         const float* d_beta, float eps, int relu, int training, void* d_dx, int out_fp32,
+                         float* d_dgamma, float* d_dbeta, const void* d_addend, int64_t M, int C, void* d_ws,
+                         hipStream_t st) {
+  const int rc = bn_bwd_reduce_run(static_cast<const T*>(d_x), static_cast<const T*>(d_dy), d_mean, d_var, d_gamma, d_beta,
+                                   eps, relu, d_dgamma, d_dbeta, M, C, d_ws, st);
+  if (rc != WSIS_OK || !d_dx) return rc;
+  return bn_bwd_apply_lp_run<T>(d_x, d_dy, d_mean, d_var, d_gamma, d_beta, d_dgamma, d_dbeta, d_addend, eps, relu, training,
+                                d_dx, out_fp32, M, C, st);
 }
 
 // ticket row of a two-level reduction: the caller's sync slot (nullptr without one, or with WSIS_BN_TICKET=0: the finish
@@ -1200,6 +1211,79 @@ static BnCentredPlan bn_centred_plan(int64_t n_part, int C, void* d_ws, int64_t 
 static bool bn_small_fused_ok(const BnCentredPlan& p, int C, std::initializer_list<const void*> rows) {
   return p.G <= bn_small_gmax() && (p.G == 1 || p.tickets) && (C & 3) == 0 && bn_small_fused_on() && bn_aligned16(rows);
 }
+
+// ---- statistics shared across ranks (wsis_bn_sync_*): what a synced layer does on either side of its collective, one
+// thread per channel, fp64, the ranks in ascending order -- every operation an IEEE + - * / or a rounding cast
+// (-ffp-contract=off), so a host restatement of the same expressions gives the same bits
+constexpr int BN_SYNC_THREADS = 64;
+
+__global__ __launch_bounds__(BN_SYNC_THREADS) void bn_sync_pack_kernel(const float* __restrict__ mean,
+                                                                       const float* __restrict__ var, int64_t M, int C,
+                                                                       double* __restrict__ out) {
+  const int c = blockIdx.x * BN_SYNC_THREADS + threadIdx.x;
+  if (c >= C) return;
+  out[c] = M > 0 ? (double)mean[c] : 0.0;
+  out[C + c] = M > 0 ? (double)var[c] : 0.0;
+  if (c == 0) out[2 * C] = (double)M;
+}
+
+__global__ __launch_bounds__(BN_SYNC_THREADS) void bn_sync_combine_kernel(const double* __restrict__ g, int R, int C,
+                                                                          float* __restrict__ mean, float* __restrict__ var,
+                                                                          float* __restrict__ running_mean,
+                                                                          float* __restrict__ running_var, float momentum,
+                                                                          double* __restrict__ count) {
+  const int c = blockIdx.x * BN_SYNC_THREADS + threadIdx.x;
+  if (c >= C) return;
+  const int64_t P = 2 * (int64_t)C + 1;      // one rank's row: mean[C], var[C], rows
+  double N = g[2 * C];
+  for (int r = 1; r < R; ++r) N += g[r * P + 2 * C];
+  if (c == 0) count[0] = N;
+  if (!(N > 0.0)) {      // no rank holds a row: nothing to normalise, the running statistics stay
+    mean[c] = 0.0f;
+    var[c] = 0.0f;
+    return;
+  }
+  double s = g[c] * g[2 * C];
+  for (int r = 1; r < R; ++r) s += g[r * P + c] * g[r * P + 2 * C];
+  const double mean64 = s / N;
+  double q = 0.0;
+  for (int r = 0; r < R; ++r) {
+    const double dm = g[r * P + c] - mean64;
+    const double t = (g[r * P + C + c] + dm * dm) * g[r * P + 2 * C];
+    q = r == 0 ? t : q + t;
+  }
+  const double var64 = q / N;
+  const float m32 = (float)mean64;
+  mean[c] = m32;
+  var[c] = (float)var64;
+  if (running_mean) {
+    const double n1 = N - 1.0 > 1.0 ? N - 1.0 : 1.0;
+    running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * m32;
+    running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)(var64 * N / n1);
+  }
+}
+
+__global__ __launch_bounds__(BN_SYNC_THREADS) void bn_sync_sums_pack_kernel(const float* __restrict__ dgamma,
+                                                                            const float* __restrict__ dbeta, int C,
+                                                                            double* __restrict__ out) {
+  const int c = blockIdx.x * BN_SYNC_THREADS + threadIdx.x;
+  if (c >= C) return;
+  out[c] = dgamma ? (double)dgamma[c] : 0.0;
+  out[C + c] = dbeta ? (double)dbeta[c] : 0.0;
+}
+
+__global__ __launch_bounds__(BN_SYNC_THREADS) void bn_sync_sums_scale_kernel(const double* __restrict__ sums, int64_t M,
+                                                                             const double* __restrict__ count, int C,
+                                                                             float* __restrict__ sum_dz_xhat,
+                                                                             float* __restrict__ sum_dz) {
+  const int c = blockIdx.x * BN_SYNC_THREADS + threadIdx.x;
+  if (c >= C) return;
+  const double k = (double)M / count[0];      // the apply pass divides by the local row count
+  sum_dz_xhat[c] = (float)(sums[c] * k);
+  sum_dz[c] = (float)(sums[C + c] * k);
+}
+
+inline unsigned bn_sync_grid(int C) { return (unsigned)((C + BN_SYNC_THREADS - 1) / BN_SYNC_THREADS); }
 
 }  // namespace
 
@@ -1488,6 +1572,56 @@ int wsis_bn_bwd_lp(const void* d_x, const void* d_dy, const float* d_mean, const
                                  d_dbeta, d_addend, M, C, d_ws, st);
   return bn_bwd_lp_run<_Float16>(d_x, d_dy, d_mean, d_var, d_gamma, d_beta, eps, relu, training, d_dx, out_fp32, d_dgamma,
                                  d_dbeta, d_addend, M, C, d_ws, st);
+}
+
+int wsis_bn_bwd_apply_lp(const void* d_x, const void* d_dy, const float* d_mean, const float* d_var, const float* d_gamma,
+                         const float* d_beta, const float* d_sum_dz_xhat, const float* d_sum_dz, float eps, int32_t relu,
+                         void* d_dx, int32_t out_fp32, const void* d_addend, int64_t M, int32_t C, int32_t dtype,
+                         void* stream) {
+  WSIS_REQUIRE(M >= 1 && C >= 1 && d_x && d_dy && d_mean && d_var && d_sum_dz_xhat && d_sum_dz && d_dx, "bad args");
+  WSIS_REQUIRE(bn_lp_domain(C, dtype, {d_x, d_dy, d_dx, d_addend}),
+               "16-bit BatchNorm: dtype 0 / 1, C % 8 == 0, C <= 1024, 16-byte aligned tensors");
+  hipStream_t st = as_stream(stream);
+  if (dtype == 0)
+    return bn_bwd_apply_lp_run<__bf16>(d_x, d_dy, d_mean, d_var, d_gamma, d_beta, d_sum_dz_xhat, d_sum_dz, d_addend, eps,
+                                       relu, 1, d_dx, out_fp32, M, C, st);
+  return bn_bwd_apply_lp_run<_Float16>(d_x, d_dy, d_mean, d_var, d_gamma, d_beta, d_sum_dz_xhat, d_sum_dz, d_addend, eps,
+                                       relu, 1, d_dx, out_fp32, M, C, st);
+}
+
+int wsis_bn_sync_pack(const float* d_mean, const float* d_var, int64_t M, int32_t C, double* d_out, void* stream) {
+  WSIS_REQUIRE(M >= 0 && C >= 1 && d_out && (M == 0 || (d_mean && d_var)), "bad args");
+  hipLaunchKernelGGL(bn_sync_pack_kernel, dim3(bn_sync_grid(C)), dim3(BN_SYNC_THREADS), 0, as_stream(stream), d_mean, d_var,
+                     M, (int)C, d_out);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+int wsis_bn_sync_combine(const double* d_gathered, int32_t R, int32_t C, float* d_mean, float* d_var,
+                         float* d_running_mean, float* d_running_var, float momentum, double* d_count, void* stream) {
+  WSIS_REQUIRE(R >= 1 && C >= 1 && d_gathered && d_mean && d_var && d_count, "bad args");
+  WSIS_REQUIRE((d_running_mean == nullptr) == (d_running_var == nullptr), "running stats come in pairs");
+  hipLaunchKernelGGL(bn_sync_combine_kernel, dim3(bn_sync_grid(C)), dim3(BN_SYNC_THREADS), 0, as_stream(stream), d_gathered,
+                     (int)R, (int)C, d_mean, d_var, d_running_mean, d_running_var, momentum, d_count);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+int wsis_bn_sync_sums_pack(const float* d_dgamma, const float* d_dbeta, int32_t C, double* d_out, void* stream) {
+  WSIS_REQUIRE(C >= 1 && d_out, "bad args");
+  hipLaunchKernelGGL(bn_sync_sums_pack_kernel, dim3(bn_sync_grid(C)), dim3(BN_SYNC_THREADS), 0, as_stream(stream), d_dgamma,
+                     d_dbeta, (int)C, d_out);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+int wsis_bn_sync_sums_scale(const double* d_sums, int64_t M, const double* d_count, int32_t C, float* d_sum_dz_xhat,
+                            float* d_sum_dz, void* stream) {
+  WSIS_REQUIRE(M >= 0 && C >= 1 && d_sums && d_count && d_sum_dz_xhat && d_sum_dz, "bad args");
+  hipLaunchKernelGGL(bn_sync_sums_scale_kernel, dim3(bn_sync_grid(C)), dim3(BN_SYNC_THREADS), 0, as_stream(stream), d_sums, M,
+                     d_count, (int)C, d_sum_dz_xhat, d_sum_dz);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
 }
 
 int64_t wsis_sync_bytes(void) { return (int64_t)kSyncSlotsTotal * (int64_t)sizeof(SyncSlot); }

@@ -153,15 +153,20 @@ class Network(nn.Module):
             # input_conv -> unet -> output_layer recorded as an op list and issued by one native call per pass
             # (model/unet_native.py); WSIS_NATIVE_UNET=0 walks the modules instead (same kernels, same results)
             import unet_native
+            # the group a synced pass exchanges its BatchNorm statistics over: the fp32 pass, and the 16-bit training
+            # pass, which is chosen with a group present only under WSIS_NATIVE_LP_SYNC=1 (lp_train_pass_wanted)
+            group = None
+            if (sync_native and self.last_pass == "native") or (sync_bn and self.last_pass == "native_lp_train"):
+                group = next((wsis_ops.sync_group(m) for m in self.unet.modules()
+                              if isinstance(m, nn.BatchNorm1d) and wsis_ops.sync_group(m) is not None), None)
             if self.last_pass == "native":
-                group = None
-                if sync_native:
-                    group = next((wsis_ops.sync_group(m) for m in self.unet.modules()
-                                  if isinstance(m, nn.BatchNorm1d) and wsis_ops.sync_group(m) is not None), None)
                 voxel_feats = unet_native.run_unet(self, input, sync_group=group)
             else:
-                run_lp = unet_native.run_unet_lp if self.last_pass == "native_lp" else unet_native.run_unet_lp_train
-                voxel_feats = run_lp(self, input, lp_dtype, unet_native.lp_out_dtype(lp_dtype, torch.is_autocast_enabled("cuda")))
+                out_dtype = unet_native.lp_out_dtype(lp_dtype, torch.is_autocast_enabled("cuda"))
+                if self.last_pass == "native_lp":
+                    voxel_feats = unet_native.run_unet_lp(self, input, lp_dtype, out_dtype)
+                else:
+                    voxel_feats = unet_native.run_unet_lp_train(self, input, lp_dtype, out_dtype, sync_group=group)
             if branch is not None:
                 # issued behind the rulebook build of this pass on the same stream: runs while the UNet does
                 for gconv in self.ecc.gconvs:

@@ -25,7 +25,8 @@ rematerialisation pointless at these sizes), parameter gradients densely in one 
 gradients with WSIS_NATIVE_LP=1 (``lp_pass_wanted``), which runs the 16-bit forward program of
 ``UNetProgram.compiled_lp`` (``run_unet_lp``), and a training-mode pass with
 WSIS_NATIVE_LP_TRAIN=1 (``lp_train_pass_wanted``), which runs the 16-bit forward + backward programs of
-``UNetProgram.compiled_lp_train`` (``UNetLpTrainFunction``).  Both switches go through one rule
+``UNetProgram.compiled_lp_train`` (``UNetLpTrainFunction``; with a SyncBatchNorm group only
+under WSIS_NATIVE_LP_SYNC=1, then issued in parts around every layer's exchange like the fp32 pass).  Both switches go through one rule
 (``_lp_wanted``), and all three passes through one driver: ``_issue_forward`` / ``_issue_backward`` lay out the arenas,
 instantiate and run, ``_store_grads`` hands the gradients to the parameters.
 """
@@ -923,7 +924,9 @@ class UNetLpTrainFunction(Function):
     """the 16-bit training pass beside ``UNetFunction``: features [M0, Cin] -> [M0, m] of ``out_dtype`` through the
     programs of ``UNetProgram.compiled_lp_train``.  The forward arena (16-bit activations, fp32 batch statistics) lives
     until the backward pass; parameter gradients are stored as in ``UNetFunction.backward`` (fp32 views of the flat buffer;
-    parameters with ``requires_grad_(False)`` get none); the early all-reduce milestone (``prog.overlap``) is not used."""
+    parameters with ``requires_grad_(False)`` get none); the early all-reduce milestone (``prog.overlap``) is not used.
+    With ``prog.bn_sync`` set both programs are issued in parts (``_run_synced``): the same programs, the layers' 16-bit
+    synced forms between the parts."""
 
     @staticmethod
     def forward(ctx, x, prog, dtype, out_dtype, anchor=None):
@@ -933,7 +936,9 @@ class UNetLpTrainFunction(Function):
         c = prog.compiled_lp_train(dtype, out_dtype == torch.float32, need_dx)
         Mvec = prog.Mvec
         out = torch.empty((int(Mvec[0]), c.out_channels), dtype=out_dtype, device=x.device)
-        arena, _, _, fwd_lut = _issue_forward(prog, c, x32.data_ptr(), out.data_ptr(), x.device)
+        # shared BatchNorm statistics: the same programs, issued in parts around every layer (_run_synced)
+        sy = ctx.sy = prog.bn_sync.new_pass() if prog.bn_sync is not None else None
+        arena, _, _, fwd_lut = _issue_forward(prog, c, x32.data_ptr(), out.data_ptr(), x.device, sy)
         if not (torch.is_grad_enabled() and (need_dx or anchor is not None)):
             sp_ops.verify_pending_counts()      # (see UNetFunction.forward)
         ctx.prog, ctx.c, ctx.arena, ctx.fwd_lut, ctx.x32, ctx.dtype, ctx.in_dtype = prog, c, arena, fwd_lut, x32, dtype, x.dtype
@@ -946,7 +951,7 @@ class UNetLpTrainFunction(Function):
         d16 = sp_ops._aligned(d_out.to(ctx.dtype))      # the incoming gradient, cast once
         # (overlap=None: the early all-reduce milestone is not used by this pass)
         garena, gbase, boffs, ga = _issue_backward(prog, c, Mvec, ctx.fwd_lut, ctx.table_lut, ctx.x32.data_ptr(),
-                                                   d16.data_ptr(), d16.device)
+                                                   d16.data_ptr(), d16.device, ctx.sy, (ctx.arena,))
         _store_grads(prog, ga)
         dx = None
         if c.dx_id >= 0:
@@ -1062,6 +1067,63 @@ def _bn_bwd_synced(lib, op, sy, dev, st):
                                        M, C, st), "bn_bwd_apply")
 
 
+def _bn_fwd_synced_lp(lib, op, sy, dev, st):
+    """the forward form of a synced layer of the 16-bit pass: local statistics of the 16-bit x, ONE all-gather of
+    (mean, var, rows) packed and combined by one small kernel on either side (wsis_bn_sync_pack / _combine: the
+    expressions of ``_bn_fwd_synced``), apply.  A rank without rows enters the collective with zeros."""
+    import torch.distributed as dist
+    M, C, flags, code = int(op["M_in"]), int(op["Cin"]), int(op["flags"]), int(op["reserved"])
+    inp, out = [int(v) for v in op["inp"]], [int(v) for v in op["out"]]
+    x, p_mean, p_var = inp[S_BN.X], out[S_BN.MEAN], out[S_BN.VAR]
+    R = dist.get_world_size(sy.group)
+    # rows 0 .. R-1: the ranks' contributions (the all-gather writes views of them: no stack), row R: this rank's own
+    buf = torch.empty((R + 1, 2 * C + 1), dtype=torch.float64, device=dev)
+    count = torch.empty(1, dtype=torch.float64, device=dev)
+    if M > 0:
+        wsb = lib.wsis_bn_workspace_bytes(M, C)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _n.check(lib.wsis_bn_stats_lp(x, M, C, p_mean, p_var, None, None, 0.0, _n.ptr(ws), wsb, code, st), "bn_stats_lp")
+    _n.check(lib.wsis_bn_sync_pack(p_mean, p_var, M, C, _n.ptr(buf[R]), st), "bn_sync_pack")
+    dist.all_gather(list(buf[:R].unbind(0)), buf[R], group=sy.group)
+    upd = bool(flags & F_UPDATE)
+    _n.check(lib.wsis_bn_sync_combine(_n.ptr(buf), R, C, p_mean, p_var, inp[S_BN.RMEAN] if upd else None,
+                                      inp[S_BN.RVAR] if upd else None, float(op["momentum"]), _n.ptr(count), st),
+             "bn_sync_combine")
+    sy.counts[p_mean] = count
+    _n.check(lib.wsis_bn_apply_lp(x, p_mean, p_var, inp[S_BN.GAMMA] or None, inp[S_BN.BETA] or None, float(op["eps"]),
+                                  1 if flags & F_RELU else 0, out[S_BN.Y], 1 if flags & F_OUT_F32 else 0, M, C, code, st),
+             "bn_apply_lp")
+
+
+def _bn_bwd_synced_lp(lib, op, sy, dev, st):
+    """the backward form: local (sum dz xhat, sum dz) -- they stay the layer's dgamma / dbeta in the flat gradient buffer,
+    as in ``_bn_bwd_synced`` --, ONE all-reduce of their fp64 copies, dx from the global sums scaled by M / N"""
+    import torch.distributed as dist
+    S = S_BN_BWD
+    M, C, flags, code = int(op["M_in"]), int(op["Cin"]), int(op["flags"]), int(op["reserved"])
+    inp, out = [int(v) for v in op["inp"]], [int(v) for v in op["out"]]
+    eps, relu = float(op["eps"]), 1 if flags & F_RELU else 0
+    args = (inp[S.X], inp[S.DY], inp[S.MEAN], inp[S.VAR], inp[S.GAMMA] or None, inp[S.BETA] or None)
+    g = torch.empty(2 * C, dtype=torch.float64, device=dev)
+    if M > 0:
+        wsb = lib.wsis_bn_workspace_bytes(M, C)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _n.check(lib.wsis_bn_bwd_lp(*args, eps, relu, 1, None, 0, out[S.DGAMMA], out[S.DBETA], None, M, C, code, _n.ptr(ws),
+                                    wsb, st), "bn_bwd_lp")
+    else:
+        sy.view(out[S.DGAMMA], C).zero_()
+        sy.view(out[S.DBETA], C).zero_()
+    _n.check(lib.wsis_bn_sync_sums_pack(out[S.DGAMMA], out[S.DBETA], C, _n.ptr(g), st), "bn_sync_sums_pack")
+    dist.all_reduce(g, group=sy.group)
+    if M > 0:
+        sc = torch.empty(2 * C, dtype=torch.float32, device=dev)
+        _n.check(lib.wsis_bn_sync_sums_scale(_n.ptr(g), M, _n.ptr(sy.counts[inp[S.MEAN]]), C, _n.ptr(sc), _n.ptr(sc[C:]), st),
+                 "bn_sync_sums_scale")
+        _n.check(lib.wsis_bn_bwd_apply_lp(*args, _n.ptr(sc), _n.ptr(sc[C:]), eps, relu, out[S.DX],
+                                          1 if flags & F_OUT_F32 else 0, inp[S.ADDEND] or None, M, C, code, st),
+                 "bn_bwd_apply_lp")
+
+
 def _run_synced(lib, ops, device, sy):
     n = len(ops)
     base, item = ops.ctypes.data, ops.dtype.itemsize
@@ -1092,7 +1154,10 @@ def _run_synced(lib, ops, device, sy):
                 keep.append(ws)
                 _n.check(lib.wsis_run_ops_part(p, j - i, _n.ptr(ws), wsb, sync, st, 0), "run_ops_part")
             if j < n:
-                if int(kinds[j]) == OP_BN_RELU:
+                fwd, lp = int(kinds[j]) == OP_BN_RELU, bool(int(flags[j]) & F_LP)
+                if lp:      # a layer of the 16-bit pass: its own forms, the exchange in one small kernel per side
+                    (_bn_fwd_synced_lp if fwd else _bn_bwd_synced_lp)(lib, ops[j], sy, device, st)
+                elif fwd:
                     _bn_fwd_synced(lib, ops[j], sy, device, st, sync)
                 else:
                     _bn_bwd_synced(lib, ops[j], sy, device, st)
@@ -1170,13 +1235,16 @@ def lp_pass_wanted(env, compute_dtype, grad_enabled, params_fp32, bn_eval, in_do
 def lp_train_pass_wanted(env, compute_dtype, grad_enabled, params_fp32, bn_train, in_domain, synced):
     """does ``Network.forward`` take the 16-bit native TRAINING pass?  ``env``: the environment (WSIS_NATIVE_LP_TRAIN=1
     switches it on, WSIS_NATIVE_UNET=0 off), ``compute_dtype`` / ``grad_enabled`` as for ``lp_pass_wanted``; then, each a
-    bool or a callable that returns one: ``synced``: a SyncBatchNorm group is present (the pass has no 16-bit form of the
-    statistics exchange), ``params_fp32`` (``lp_params_fp32``), ``bn_train``: every BatchNorm layer of the UNet in
-    training mode with running statistics (``lp_bn_train``), ``in_domain``: every forward, dIn and dW product inside
-    spconv.ops.lp_supported (``lp_train_in_domain``).  The cheap conditions come first: a callable runs only when
+    bool or a callable that returns one: ``synced``: a SyncBatchNorm group is present -- that refuses the pass unless
+    WSIS_NATIVE_LP_SYNC=1 opts into its synced form (the statistics exchange between the parts of the pass,
+    ``_bn_fwd_synced_lp`` / ``_bn_bwd_synced_lp``; with the switch the group is not asked for here: ``Network.forward``
+    hands it to ``run_unet_lp_train``) --, ``params_fp32`` (``lp_params_fp32``), ``bn_train``: every BatchNorm layer of
+    the UNet in training mode with running statistics (``lp_bn_train``), ``in_domain``: every forward, dIn and dW product
+    inside spconv.ops.lp_supported (``lp_train_in_domain``).  The cheap conditions come first: a callable runs only when
     everything in front of it holds.  Pure: no device."""
+    sync_ok = lambda: env.get("WSIS_NATIVE_LP_SYNC", "0") == "1" or not _holds(synced)      # noqa: E731
     return _lp_wanted(env, "WSIS_NATIVE_LP_TRAIN", compute_dtype, grad_enabled, True,
-                      (lambda: not _holds(synced), params_fp32, bn_train, in_domain))
+                      (sync_ok, params_fp32, bn_train, in_domain))
 
 
 def _holds(check):
@@ -1287,12 +1355,21 @@ def run_unet_lp(net, input_tensor, dtype, out_dtype):
     return out
 
 
-def run_unet_lp_train(net, input_tensor, dtype, out_dtype):
+def _select_bn_sync(prog, sync_group):
+    """the program's _BnSync for ``sync_group`` (None: per-rank statistics), kept while the group stays the same"""
+    if sync_group is None:
+        prog.bn_sync = None
+    elif prog.bn_sync is None or prog.bn_sync.group is not sync_group:
+        prog.bn_sync = _BnSync(prog, sync_group)
+
+
+def run_unet_lp_train(net, input_tensor, dtype, out_dtype, sync_group=None):
     """the 16-bit training pass of input_conv + unet + output_layer: features -> [M0, m] of ``out_dtype`` with a
-    backward pass (``UNetLpTrainFunction``; rounding contract: DESIGN.md section 10.2)"""
+    backward pass (``UNetLpTrainFunction``; rounding contract: DESIGN.md section 10.2).  ``sync_group``: the process group
+    the BatchNorm layers take their batch statistics over (None: per rank)"""
     _check_experimental_switches()
     prog = _program(net)
-    prog.bn_sync = None
+    _select_bn_sync(prog, sync_group)
     prog.bind(input_tensor)
     anchor = next((p for p in prog.params if p.requires_grad), None)
     return UNetLpTrainFunction.apply(input_tensor.features, prog, dtype, out_dtype, anchor)
@@ -1303,10 +1380,7 @@ def run_unet(net, input_tensor, sync_group=None):
     ``sync_group``: the process group the BatchNorm layers take their batch statistics over (None: per rank)"""
     _check_experimental_switches()
     prog = _program(net)
-    if sync_group is None:
-        prog.bn_sync = None
-    elif prog.bn_sync is None or prog.bn_sync.group is not sync_group:
-        prog.bn_sync = _BnSync(prog, sync_group)
+    _select_bn_sync(prog, sync_group)
     prog.bind(input_tensor)
     anchor = next((p for p in prog.params if p.requires_grad), None) if torch.is_grad_enabled() else None
     return UNetFunction.apply(input_tensor.features, prog, anchor)

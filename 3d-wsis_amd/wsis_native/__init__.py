@@ -114,6 +114,11 @@ _HIP_SIGS = {
     "wsis_bn_stats_lp": (I32, [P, I64, I32, P, P, P, P, F32, P, I64, I32, P]),
     "wsis_bn_bwd_lp": (I32, [P, P, P, P, P, P, F32, I32, I32, P, I32, P, P, P, I64, I32, I32, P, I64, P]),
     "wsis_bn_bwd": (I32, [P, P, P, P, P, P, F32, I32, I32, P, P, P, P, I64, I32, P, I64, P]),
+    "wsis_bn_bwd_apply_lp": (I32, [P, P, P, P, P, P, P, P, F32, I32, P, I32, P, I64, I32, I32, P]),
+    "wsis_bn_sync_pack": (I32, [P, P, I64, I32, P, P]),
+    "wsis_bn_sync_combine": (I32, [P, I32, I32, P, P, P, P, F32, P, P]),
+    "wsis_bn_sync_sums_pack": (I32, [P, P, I32, P, P]),
+    "wsis_bn_sync_sums_scale": (I32, [P, I64, P, I32, P, P, P]),
     "wsis_segment_csr_workspace_bytes": (I64, [I64, I64]),
     "wsis_segment_csr": (I32, [P, I64, I64, P, P, P, I64, P]),
     "wsis_segment_csr_batch_workspace_bytes": (I64, [I64]),

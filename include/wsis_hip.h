@@ -457,6 +457,37 @@ int wsis_bn_bwd(const float* d_x, const float* d_dy, const float* d_mean, const 
 int wsis_bn_bwd_apply(const float* d_x, const float* d_dy, const float* d_mean, const float* d_var,
                       const float* d_gamma, const float* d_beta, const float* d_sum_dz_xhat, const float* d_sum_dz,
                       float eps, int32_t relu, float* d_dx, const float* d_addend, int64_t M, int32_t C, void* stream);
+/* wsis_bn_bwd_apply for 16-bit x, dy and (optional) addend (dtype 0 = bf16, 1 = fp16): the apply pass of wsis_bn_bwd_lp
+ * alone, from reduced fp32 sums.  dx is rounded ONCE to 16 bits, or stored as fp32 when out_fp32 (then it equals
+ * wsis_bn_bwd_apply on the widened inputs bit for bit).  Fed the dgamma / dbeta that wsis_bn_bwd_lp(d_dx = NULL) wrote,
+ * dx equals wsis_bn_bwd_lp's own bit for bit.  Domain as wsis_bn_stats_lp (all tensors 16-byte aligned); no workspace. */
+int wsis_bn_bwd_apply_lp(const void* d_x, const void* d_dy, const float* d_mean, const float* d_var, const float* d_gamma,
+                         const float* d_beta, const float* d_sum_dz_xhat, const float* d_sum_dz, float eps, int32_t relu,
+                         void* d_dx, int32_t out_fp32, const void* d_addend, int64_t M, int32_t C, int32_t dtype,
+                         void* stream);
+
+/* ---- the statistics exchange of a BatchNorm layer shared across R ranks, one small launch per side of the collective.
+ * One thread per channel, fp64, the ranks in ascending order, no atomics: every operation is an IEEE + - * / or a
+ * round-to-nearest cast, so the results are the bits a host restatement of the expressions below gives.
+ *
+ * wsis_bn_sync_pack: what a rank contributes to the all-gather, d_out fp64 [2C + 1] = mean[C], var[C], (double)M of its M
+ * local rows.  M == 0 (a rank without rows still enters the collective): zeros, neither pointer is read. */
+int wsis_bn_sync_pack(const float* d_mean, const float* d_var, int64_t M, int32_t C, double* d_out, void* stream);
+/* wsis_bn_sync_combine: d_gathered fp64 [R][2C + 1] (rank r's wsis_bn_sync_pack in row r) -> statistics over all rows,
+ *   N = sum_r n_r,  mean64 = (sum_r m_r n_r) / N,  var64 = (sum_r (v_r + (m_r - mean64)^2) n_r) / N   (sums in ascending r)
+ * stored as fp32 d_mean / d_var; d_count[0] = N (fp64, stays on the device for wsis_bn_sync_sums_scale).  With the
+ * running pair: rm = (1 - momentum) rm + momentum mean,  rv = (1 - momentum) rv + momentum float(var64 N / max(N - 1, 1))
+ * in fp32.  N == 0 (no rank holds a row): mean = var = 0, the running pair stays. */
+int wsis_bn_sync_combine(const double* d_gathered, int32_t R, int32_t C, float* d_mean, float* d_var,
+                         float* d_running_mean, float* d_running_var, float momentum, double* d_count, void* stream);
+/* wsis_bn_sync_sums_pack: the local sums of wsis_bn_bwd / wsis_bn_bwd_lp (d_dx = NULL) widened for the all-reduce, d_out
+ * fp64 [2C] = dgamma[C], dbeta[C]; a NULL input (a rank without rows) gives zeros. */
+int wsis_bn_sync_sums_pack(const float* d_dgamma, const float* d_dbeta, int32_t C, double* d_out, void* stream);
+/* wsis_bn_sync_sums_scale: the all-reduced d_sums fp64 [2C] as the fp32 arguments of wsis_bn_bwd_apply(_lp), which
+ * divides by the LOCAL row count M: d_sum_dz_xhat[c] = float(d_sums[c] * ((double)M / d_count[0])), d_sum_dz[c] likewise
+ * from d_sums[C + c]. */
+int wsis_bn_sync_sums_scale(const double* d_sums, int64_t M, const double* d_count, int32_t C, float* d_sum_dz_xhat,
+                            float* d_sum_dz, void* stream);
 
 /* ---- a14/a15: row gather and torch_scatter.scatter  backbone_3D_WSIS.py:179,188,225,232,244 --
  * CSR of a (possibly unsorted) index vector: d_perm int32 [N] = stable argsort(index),
