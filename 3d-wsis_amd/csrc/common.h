@@ -208,17 +208,19 @@ int spconv_ring_launch(int nt, const float* d_X, const int32_t* d_nbr, const int
                        unsigned* d_err, int64_t M_in, int64_t M_out, int K, int Cin, int Cout, hipEvent_t ka, hipEvent_t kb, hipStream_t st,
                        unsigned long long* d_dbg = nullptr);
 
-// wave-autonomous weight-gradient kernel (csrc/spconv_dw2.hip), dispatched from wsis_spconv_dw
-bool dw2_supported(int K, int Cin, int Cout);
-bool dw2_fits(int64_t M_in, int64_t M_out, int K, int Cin, int Cout);   // 32-bit buffer offsets
-int64_t dw2_workspace_bytes(int64_t M_out, int K, int Cin, int Cout);
+// round-1 weight-gradient kernel (csrc/spconv.hip), dispatched from csrc/spconv_dw2.hip: the launcher closes the main part
+// of the profile record (prof.stop()) between its main launches and its slab sum
+int64_t spconv_dw1_workspace_bytes(int64_t M_out, int K, int Cin, int Cout);      // -1: more than 128 offsets
+int spconv_dw1_launch(const float* d_X, const int32_t* d_nbr, const int32_t* d_order, const float* d_dY, float* d_dW,
+                      int64_t M_in, int64_t M_out, int K, int Cin, int Cout, void* d_ws, ProfScope& prof, hipStream_t st);
+
+// what the op-list executor uses of the weight-gradient dispatch (csrc/spconv_dw2.hip)
 void dw2_set_batch_rows(int64_t rows);      // launch-plan hint of the weight-gradient launches (wsis_hint_batch_rows)
 int64_t dw2_batch_rows();                   // the hint as last set (0: none)
-// Deferred slab sums (the op-list executor, round 6): with a record slot set for the calling thread, dw2_launch /
-// dw2_launch_swapped issue the main kernel only and describe the fixed-order slab sum that finishes the product in the
-// slot; the executor finishes all products of (a part of) a backward pass with ONE dw2_reduce_batch launch -- same
-// arithmetic and order per product as the per-launch sum (bit-identical), without 55 launches of a few microseconds
-// each.  The slabs of every deferred product need their own workspace until that launch has run.
+// Deferred slab sums: with a record slot set for the calling thread, a product of the wave-autonomous kernels issues its
+// main kernel only and describes the fixed-order slab sum that finishes it in the slot; the executor finishes all
+// products of (a part of) a backward pass with ONE dw2_reduce_batch launch -- same arithmetic and order per product as
+// the per-launch sum (bit-identical).  The slabs of every deferred product need their own workspace until then.
 struct DwRedRec {
   const float* partial = nullptr;      // nullptr: the product finished itself (shape outside the dw2 kernel, empty level)
   float* dW = nullptr;
@@ -227,11 +229,6 @@ struct DwRedRec {
 };
 void dw2_set_defer(DwRedRec* slot);    // thread-local; nullptr switches deferral off
 int dw2_reduce_batch(const DwRedRec* recs, int n, hipStream_t st);
-int dw2_launch(const float* d_X, const int32_t* d_nbr, const int32_t* d_order, const float* d_dY, float* d_dW,
-               int64_t M_in, int64_t M_out, int K, int Cin, int Cout, void* d_ws, hipStream_t st);
-int dw2_launch_swapped(const float* d_X, const float* d_mean, const float* d_var, const float* d_gamma, const float* d_beta,
-                       float eps, int relu, const int32_t* d_nbr_b, const int32_t* d_order_b, int flip, const float* d_dY,
-                       float* d_dW, int64_t M_in, int64_t M_out, int K, int Cin, int Cout, void* d_ws, hipStream_t st);
 
 // row / column of element t of a row-major [rows, C] tensor without a 64-bit division per element: a runtime int64
 // division is ~100 instructions on this ISA -- in segment_bwd_kernel it, not HBM, set the time (21 us for 25 MB).

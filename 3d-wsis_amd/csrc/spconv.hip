@@ -1,7 +1,8 @@
 // Sparse convolution on the gather-table rulebook.
 //
 //   out[r,:] = sum_k X[nbr[k][r],:] @ W[k]          (wsis_spconv_fwd; also every dIn pass)
-//   dW[k]    = sum_r X[nbr[k][r],:]^T (x) dY[r,:]   (wsis_spconv_dw)
+//   dW[k]    = sum_r X[nbr[k][r],:]^T (x) dY[r,:]   (spconv_dw1_launch: the generic kernel behind wsis_spconv_dw, which
+//                                                    csrc/spconv_dw2.hip dispatches)
 //
 // Output-stationary implicit GEMM.  A workgroup owns a tile of 128 output rows *in tile order* (rows
 // sorted by their set of active kernel offsets, wsis_mask_order), reads the tile's slice of the packed
@@ -573,7 +574,7 @@ __global__ void weight_transpose_kernel(const float* __restrict__ W, float* __re
 // kernels (2x2x2 strided, 1x1x1) use equal chunks.  Each item writes one [ci_pad][Cout] slab; dw_reduce_kernel
 // adds the slabs of an offset in item order (fixed order -> deterministic).
 constexpr int DW_MAX_K = 128;
-struct DwPlan {
+struct DwItems {
   int begin[DW_MAX_K + 1];   // items of offset k: [begin[k], begin[k+1])
 };
 
@@ -581,7 +582,7 @@ template <int NBO, bool DIAG = false>
 __global__ __launch_bounds__(256) void spconv_dw_kernel(
     const float* __restrict__ X, const int32_t* __restrict__ nbrS, const int32_t* __restrict__ order,
     const float* __restrict__ dY, float* __restrict__ partial, int64_t M_in, int64_t M_out, int K, int Cin,
-    int Cout, DwPlan plan, int n_cib, int co0, unsigned long long* __restrict__ dbg = nullptr) {
+    int Cout, DwItems plan, int n_cib, int co0, unsigned long long* __restrict__ dbg = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float red[];  // [4][NBO][1024]
   // DIAG build only: per-phase cycle sums (s_memtime) of every wave, dbg[(item*4 + wave)*8 + phase]
   unsigned long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -740,7 +741,7 @@ __global__ __launch_bounds__(256) void spconv_dw_kernel(
   }
 }
 
-__global__ void dw_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dW, DwPlan plan, int K,
+__global__ void dw_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dW, DwItems plan, int K,
                                  int Cin, int Cout, int ci_pad) {
   const int64_t total = (int64_t)K * Cin * Cout;
   const int64_t slab = (int64_t)ci_pad * Cout;
@@ -760,7 +761,7 @@ __global__ void dw_reduce_kernel(const float* __restrict__ partial, float* __res
 }
 
 // four output channels per thread (Cout % 4 == 0, aligned dW): the slab walk issues eight 16-byte loads at a time
-__global__ void dw_reduce4_kernel(const float4* __restrict__ partial, float4* __restrict__ dW, DwPlan plan, int K,
+__global__ void dw_reduce4_kernel(const float4* __restrict__ partial, float4* __restrict__ dW, DwItems plan, int K,
                                   int Cin, int cout4, int ci_pad) {
   const int64_t total4 = (int64_t)K * Cin * cout4;
   const int64_t slab4 = (int64_t)ci_pad * cout4;
@@ -796,7 +797,7 @@ int dw_base_chunks(int64_t M_out) {
   return (int)c;
 }
 
-void dw_make_plan(int64_t M_out, int K, DwPlan& plan) {
+void dw_make_items(int64_t M_out, int K, DwItems& plan) {
   const int base = dw_base_chunks(M_out);
   const int64_t max_chunks = M_out <= 0 ? 1 : ceil_div(M_out, 256);   // >= 64 rows per wave
   plan.begin[0] = 0;
@@ -814,6 +815,66 @@ void dw_make_plan(int64_t M_out, int K, DwPlan& plan) {
 }
 
 }  // namespace
+
+// the round-1 weight-gradient kernel as the dispatch of csrc/spconv_dw2.hip sees it: a size function and a launcher
+// (main launches, prof.stop(), fixed-order slab sum)
+namespace wsis {
+
+int64_t spconv_dw1_workspace_bytes(int64_t M_out, int K, int Cin, int Cout) {
+  if (K > DW_MAX_K) return -1;
+  DwItems plan;
+  dw_make_items(M_out, K, plan);
+  const int64_t ci_pad = ceil_div(Cin, 32) * 32;
+  return (int64_t)plan.begin[K] * ci_pad * Cout * (int64_t)sizeof(float) + 256;
+}
+
+int spconv_dw1_launch(const float* d_X, const int32_t* d_nbr, const int32_t* d_order, const float* d_dY, float* d_dW,
+                      int64_t M_in, int64_t M_out, int K, int Cin, int Cout, void* d_ws, ProfScope& prof, hipStream_t st) {
+  WSIS_REQUIRE(K <= DW_MAX_K, "dW supports kernel volumes up to 128 offsets");
+  DwItems plan;
+  dw_make_items(M_out, K, plan);
+  const int n_cib = (int)ceil_div(Cin, 32);
+  const int ci_pad = n_cib * 32;
+  float* partial = static_cast<float*>(d_ws);
+  const int nblk = (Cout + 31) / 32;
+  const dim3 grid((unsigned)plan.begin[K], (unsigned)n_cib, 1);
+  // output-channel blocks are processed in groups of <= 5 per launch (register budget)
+  for (int cb0 = 0; cb0 < nblk; cb0 += 5) {
+    const int nbo = min(5, nblk - cb0);
+    const int co0 = cb0 * 32;
+    const size_t lds = (size_t)4 * nbo * 1024 * sizeof(float);
+#define WSIS_DW_CASE(n)                                                                                  \
+  case n:                                                                                                \
+    WSIS_HIP_CHECK(hipFuncSetAttribute((const void*)spconv_dw_kernel<n, false>,                          \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
+    hipLaunchKernelGGL((spconv_dw_kernel<n, false>), grid, dim3(256), lds, st, d_X, d_nbr, d_order, d_dY, \
+                       partial, M_in, M_out, K, Cin, Cout, plan, n_cib, co0, nullptr);                   \
+    break;
+    switch (nbo) {
+      WSIS_DW_CASE(1)
+      WSIS_DW_CASE(2)
+      WSIS_DW_CASE(3)
+      WSIS_DW_CASE(4)
+      WSIS_DW_CASE(5)
+    }
+#undef WSIS_DW_CASE
+    WSIS_LAUNCH_CHECK();
+  }
+  prof.stop();
+  const int64_t total = (int64_t)K * Cin * Cout;
+  if ((Cout & 3) == 0 && ((reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(d_dW)) & 15) == 0) {
+    hipLaunchKernelGGL(dw_reduce4_kernel, dim3(grid_for(total / 4, 256)), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(partial), reinterpret_cast<float4*>(d_dW), plan, K, Cin, Cout / 4,
+                       ci_pad);
+  } else {
+    hipLaunchKernelGGL(dw_reduce_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, partial, d_dW, plan, K, Cin,
+                       Cout, ci_pad);
+  }
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+}  // namespace wsis
 
 extern "C" {
 
@@ -1010,8 +1071,8 @@ int wsis_debug_dw_diag(const float* d_X, const int32_t* d_nbr, const int32_t* d_
                        float* d_partial, int64_t M_in, int64_t M_out, int32_t K, int32_t Cin, int32_t Cout,
                        unsigned long long* d_dbg, int32_t* n_items, void* stream) {
   WSIS_REQUIRE(K <= DW_MAX_K && Cout <= 64 && n_items, "diag supports Cout <= 64");
-  DwPlan plan;
-  dw_make_plan(M_out, K, plan);
+  DwItems plan;
+  dw_make_items(M_out, K, plan);
   *n_items = plan.begin[K];
   if (!d_dbg) return WSIS_OK;
   const int n_cib = (int)ceil_div(Cin, 32);
@@ -1035,127 +1096,6 @@ int wsis_weight_transpose(const float* d_W, float* d_WT, int32_t K, int32_t Cin,
   const int64_t total = (int64_t)K * Cin * Cout;
   hipLaunchKernelGGL(weight_transpose_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream),
                      d_W, d_WT, K, Cin, Cout, flip);
-  WSIS_LAUNCH_CHECK();
-  return WSIS_OK;
-}
-
-int64_t wsis_spconv_dw_workspace_bytes(int64_t M_out, int32_t K, int32_t Cin, int32_t Cout) {
-  if (M_out < 0 || K < 1 || Cin < 1 || Cout < 1) return -1;
-  if (K > DW_MAX_K) return -1;
-  DwPlan plan;
-  dw_make_plan(M_out, K, plan);
-  const int64_t ci_pad = ceil_div(Cin, 32) * 32;
-  const int64_t old_bytes = (int64_t)plan.begin[K] * ci_pad * Cout * (int64_t)sizeof(float) + 256;
-  if (dw2_supported(K, Cin, Cout)) return std::max(old_bytes, dw2_workspace_bytes(M_out, K, Cin, Cout));
-  if (spconv_in_supported(K, Cin, Cout)) return std::max(old_bytes, spconv_in_dw_workspace_bytes(M_out));
-  return old_bytes;
-}
-
-int32_t wsis_spconv_dw_bn_supported(int32_t K, int32_t Cin, int32_t Cout) {
-  return (dw2_supported(K, Cout, Cin) && Cin % 32 == 0 && Cout % 32 == 0) ? 1 : 0;
-}
-
-int64_t wsis_spconv_dw_bn_workspace_bytes(int64_t M_in, int32_t K, int32_t Cin, int32_t Cout) {
-  if (M_in < 0 || !wsis_spconv_dw_bn_supported(K, Cin, Cout)) return -1;
-  return dw2_workspace_bytes(M_in, K, Cout, Cin);
-}
-
-int wsis_spconv_dw_bn(const float* d_X, const float* d_mean, const float* d_var, const float* d_gamma,
-                      const float* d_beta, float eps, int32_t relu, const int32_t* d_nbr_b, const int32_t* d_order_b,
-                      int32_t flip, const float* d_dY, float* d_dW, int64_t M_in, int64_t M_out, int32_t K, int32_t Cin,
-                      int32_t Cout, void* d_ws, int64_t ws_bytes, void* stream) {
-  WSIS_REQUIRE(M_in >= 0 && M_out >= 0 && d_dW, "bad args");
-  WSIS_REQUIRE(wsis_spconv_dw_bn_supported(K, Cin, Cout), "needs K <= 32 and channel counts that are multiples of 32");
-  hipStream_t st = as_stream(stream);
-  if (M_in == 0 || M_out == 0) {
-    WSIS_HIP_CHECK(hipMemsetAsync(d_dW, 0, sizeof(float) * (size_t)K * Cin * Cout, st));
-    return WSIS_OK;
-  }
-  WSIS_REQUIRE(d_X && d_dY && d_ws && d_nbr_b && d_order_b, "null pointer");
-  WSIS_REQUIRE((d_mean == nullptr) == (d_var == nullptr), "mean and var come in pairs");
-  WSIS_REQUIRE(dw2_fits(M_out, M_in, K, Cout, Cin), "tensor too large for 32-bit gather offsets");
-  WSIS_REQUIRE(ws_bytes >= wsis_spconv_dw_bn_workspace_bytes(M_in, K, Cin, Cout), "workspace too small");
-  WSIS_REQUIRE(((reinterpret_cast<uintptr_t>(d_X) | reinterpret_cast<uintptr_t>(d_dY) | reinterpret_cast<uintptr_t>(d_dW) |
-                 reinterpret_cast<uintptr_t>(d_ws)) & 15) == 0, "16-byte alignment");
-  return dw2_launch_swapped(d_X, d_mean, d_var, d_gamma, d_beta, eps, (int)relu, d_nbr_b, d_order_b, (int)flip, d_dY, d_dW,
-                            M_in, M_out, K, Cin, Cout, d_ws, st);
-}
-
-int wsis_hint_batch_rows(int64_t rows) {
-  WSIS_REQUIRE(rows >= 0, "bad row count");
-  dw2_set_batch_rows(rows);
-  return WSIS_OK;
-}
-
-int wsis_spconv_dw(const float* d_X, const int32_t* d_nbr, const int32_t* d_order, const float* d_dY,
-                   float* d_dW, int64_t M_in, int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, void* d_ws,
-                   int64_t ws_bytes, void* stream) {
-  WSIS_REQUIRE(M_in >= 0 && M_out >= 0 && K >= 1 && Cin >= 1 && Cout >= 1 && d_dW, "bad args");
-  hipStream_t st = as_stream(stream);
-  if (M_out == 0) {
-    WSIS_HIP_CHECK(hipMemsetAsync(d_dW, 0, sizeof(float) * (size_t)K * Cin * Cout, st));
-    return WSIS_OK;
-  }
-  WSIS_REQUIRE(d_X && d_dY && d_ws, "null pointer");
-  WSIS_REQUIRE(d_nbr || (K == 1 && M_in == M_out), "nbr may be null only for the dense 1x1 case");
-  WSIS_REQUIRE(K <= DW_MAX_K, "dW supports kernel volumes up to 128 offsets");
-  WSIS_REQUIRE(M_in * Cin * 4 < ((int64_t)1 << 32) && M_out * Cout * 4 < ((int64_t)1 << 32),
-               "dW addresses features as 32-bit byte offsets: a feature matrix must stay below 4 GiB");
-  WSIS_REQUIRE(ws_bytes >= wsis_spconv_dw_workspace_bytes(M_out, K, Cin, Cout), "workspace too small");
-  if (dw2_supported(K, Cin, Cout) && dw2_fits(M_in, M_out, K, Cin, Cout) &&
-      ((d_nbr && d_order) || (!d_nbr && K == 1 && M_in == M_out)) && ((reinterpret_cast<uintptr_t>(d_X) | reinterpret_cast<uintptr_t>(d_dY) |
-                                       reinterpret_cast<uintptr_t>(d_dW) | reinterpret_cast<uintptr_t>(d_ws)) & 15) == 0)
-    return dw2_launch(d_X, d_nbr, d_order, d_dY, d_dW, M_in, M_out, K, Cin, Cout, d_ws, st);
-  if (d_nbr && spconv_in_supported(K, Cin, Cout) &&
-      ((reinterpret_cast<uintptr_t>(d_X) & 7) | (reinterpret_cast<uintptr_t>(d_dW) & 15) | (reinterpret_cast<uintptr_t>(d_ws) & 15)) == 0) {
-    // the 6-channel input convolution: im2col on the matrix cores (csrc/spconv_in.hip)
-    ProfScope prof_in(1, st, true);
-    const int rc = spconv_in_dw_launch(d_X, d_nbr, d_order, d_dY, d_dW, M_out, d_ws, prof_in.ka(), prof_in.kb(), st);
-    prof_in.stop();
-    prof_in.tail();
-    return rc;
-  }
-  DwPlan plan;
-  dw_make_plan(M_out, K, plan);
-  const int n_cib = (int)ceil_div(Cin, 32);
-  const int ci_pad = n_cib * 32;
-  float* partial = static_cast<float*>(d_ws);
-  const int nblk = (Cout + 31) / 32;
-  const dim3 grid((unsigned)plan.begin[K], (unsigned)n_cib, 1);
-  // output-channel blocks are processed in groups of <= 5 per launch (register budget)
-  ProfScope prof(1, st);
-  for (int cb0 = 0; cb0 < nblk; cb0 += 5) {
-    const int nbo = min(5, nblk - cb0);
-    const int co0 = cb0 * 32;
-    const size_t lds = (size_t)4 * nbo * 1024 * sizeof(float);
-#define WSIS_DW_CASE(n)                                                                                  \
-  case n:                                                                                                \
-    WSIS_HIP_CHECK(hipFuncSetAttribute((const void*)spconv_dw_kernel<n, false>,                          \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
-    hipLaunchKernelGGL((spconv_dw_kernel<n, false>), grid, dim3(256), lds, st, d_X, d_nbr, d_order, d_dY, \
-                       partial, M_in, M_out, K, Cin, Cout, plan, n_cib, co0, nullptr);                   \
-    break;
-    switch (nbo) {
-      WSIS_DW_CASE(1)
-      WSIS_DW_CASE(2)
-      WSIS_DW_CASE(3)
-      WSIS_DW_CASE(4)
-      WSIS_DW_CASE(5)
-    }
-#undef WSIS_DW_CASE
-    WSIS_LAUNCH_CHECK();
-  }
-  prof.stop();
-  const int64_t total = (int64_t)K * Cin * Cout;
-  if ((Cout & 3) == 0 && ((reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(d_dW)) & 15) == 0) {
-    hipLaunchKernelGGL(dw_reduce4_kernel, dim3(grid_for(total / 4, 256)), dim3(256), 0, st,
-                       reinterpret_cast<const float4*>(partial), reinterpret_cast<float4*>(d_dW), plan, K, Cin, Cout / 4,
-                       ci_pad);
-  } else {
-    hipLaunchKernelGGL(dw_reduce_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, partial, d_dW, plan, K, Cin,
-                       Cout, ci_pad);
-  }
-  prof.tail();
   WSIS_LAUNCH_CHECK();
   return WSIS_OK;
 }

@@ -16,7 +16,13 @@
 // computing (counted s_waitcnt vmcnt), and the tile issue is interleaved by hand into the MFMA chain.  The 4 waves of a
 // workgroup share a combination and add their accumulators through LDS in wave order; workgroup slabs are added in
 // workgroup order by dw2_reduce_kernel: no atomics, bit-reproducible.  Dense 1x1 layers (no table) and a partial last
-// output block (Cout % 4 == 0) are covered too.  Measurements and what bounds it: DESIGN.md 4.1.
+// output block (Cout % 4 == 0) are covered too.  Measurements and what bounds it: DESIGN.md 4.2.
+//
+// This file is also the dispatch of EVERY fp32 weight gradient: the entry points wsis_spconv_dw, wsis_spconv_dw_bn, their
+// size queries and wsis_hint_batch_rows; one launch plan (dw_plan) and one launch-and-finish (dw_run) behind them.  The
+// shapes outside these kernels go to launchers declared in common.h: the 6 -> 32 input convolution (spconv_in.hip:
+// spconv_in_dw_launch) and the round-1 generic kernel (spconv.hip: spconv_dw1_launch).  The 16-bit weight gradient
+// (spconv_lp.hip) has its own kernel and plan.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -1005,34 +1011,243 @@ int dw2_P_plan(int64_t M_out, int K, int Cin, int Cout, bool wide) {
   if (P < 1) P = 1;
   return (int)P;
 }
-int dw2_P(int64_t M_out, int K, int Cin, int Cout) {
-  return dw2_P_plan(M_out, K, Cin, Cout, g_batch_rows.load(std::memory_order_relaxed) >= WIDE_ROWS);
+bool dw2_wide() { return g_batch_rows.load(std::memory_order_relaxed) >= WIDE_ROWS; }
+
+bool dw2_supported(int K, int Cin, int Cout) {
+  static const int on = dw2_env("WSIS_DW2", 1);      // (read once; the initialiser of a local static is thread-safe)
+  return on && K >= 1 && K <= 32 && Cin >= 32 && Cin % 32 == 0 && Cout >= 4 && Cout % 4 == 0;     // (16-byte dY pieces)
+}
+
+bool dw2_fits(int64_t M_in, int64_t M_out, int K, int Cin, int Cout) {      // 32-bit buffer offsets
+  const int64_t lim = (int64_t)1 << 31;
+  return M_in * Cin * 4 < lim && M_out * Cout * 4 < lim && (int64_t)K * M_out * 4 < lim && M_in >= 1 && M_out >= 1;
+}
+
+// the register-gather kernel applies when row ids fit 24 bits (v_mad_u32_u24) and a missing pair's offset
+// (0xFFFFFF x pitch mod 2^32) lies beyond the gathered tensor, so that it reads zeros
+bool dw3_fits(int64_t M_in, int Cin) {
+  const uint64_t p = (uint64_t)Cin * 4u;
+  const uint32_t w = (uint32_t)(0xFFFFFFull * p);
+  return M_in < (1 << 24) - 1 && (uint64_t)w >= (uint64_t)M_in * p && w <= 0xFFFFFF00u;
+}
+// WSIS_DW3 (read per call): 1 (default) = spconv_dw3_kernel where it fits, 0 = spconv_dw2_kernel everywhere.  Alone on the
+// GPU the two kernels are at parity (profiles/r06_dw3.txt); IN THE STEP the register-gather kernel wins because of what it
+// does not occupy: 26 KB of LDS per workgroup instead of 77 KB -- the dIn items that share its CU from the main stream
+// (37 KB each at levels 1-2, 8.4 KB at level 0) keep their occupancy: 7.77 -> 7.66 ms at one scene, 11.75 -> 11.67 at two,
+// 20.37 -> 20.06 at four (profiles/r06_ab_dw3_lds.txt; with a 66 KB epilogue the same kernel measured 20.40 vs 20.35)
+int dw3_mode() {
+  const char* e = getenv("WSIS_DW3");
+  return e ? atoi(e) : 1;
+}
+// header table block by ONE 16-byte DMA (both kernels): WSIS_DW_H16 = 1 always (default), 2 only where every table line is
+// 16-byte aligned, 0 never (EXPERIMENTAL build: live)
+bool dw3_h16(int64_t M_out) {
+  const int m = dw2_env("WSIS_DW_H16", 1);
+  return m == 1 || (m == 2 && (M_out & 3) == 0);
+}
+int dw3_flags(int64_t M_out) { return (dw3_h16(M_out) ? 1 : 0) | (dw2_env("WSIS_DW_BAL", 1) ? 2 : 0); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The launch plan of a weight gradient: ONE rule (dw_plan) for everything that sizes, launches or diagnoses one --
+// wsis_spconv_dw, wsis_spconv_dw_bn, the two size queries, wsis_debug_dw2_diag and the plan query wsis_debug_dw_plan.
+// tests/dw_plan_ref.py restates it.
+// refused (the entry point answers `why`) | no rows: dW is zero-filled | spconv_dw3_kernel (register gather) | spconv_dw2_kernel
+// (LDS ring) | with the XCD-aware deal of the slices | in the own-rows form (wsis_spconv_dw_bn) | the 6 -> 32 input
+// convolution (spconv_in.hip) | the round-1 kernel (spconv.hip)
+enum DwKind : int { DW_REFUSED = -1, DW_EMPTY, DW_DW3, DW_RING, DW_RING_XCD, DW_SWAPPED, DW_IN_CONV, DW_GENERIC };
+enum { DW_NO_TABLE = 0, DW_TABLE = 1, DW_TABLE_NO_ORDER = 2 };
+enum { DW_X16 = 1, DW_X8 = 2, DW_DY16 = 4, DW_DW16 = 8, DW_WS16 = 16, DW_ALL16 = DW_X16 | DW_DY16 | DW_DW16 | DW_WS16 };
+
+struct DwShape {
+  int64_t M_in, M_out;
+  int K, Cin, Cout;
+  int table;        // DW_NO_TABLE / DW_TABLE (with its order) / DW_TABLE_NO_ORDER
+  int align;        // DW_X16 | ...: what is known of the four pointers
+  bool swapped;     // the own-rows form
+};
+struct DwLaunch {
+  DwKind kind = DW_REFUSED;
+  const char* why = nullptr;
+  // the wave-autonomous kernels (DW_DW3 ... DW_SWAPPED; the other launchers choose their own grids):
+  int P = 0, NOG = 0;            // slabs = workgroups per combination; offset groups
+  unsigned gx = 0, gy = 0;       // grid (P, offset groups x gathered 32-channel chunks x own 32-channel blocks)
+  int64_t lds = 0;               // dynamic LDS bytes
+  int64_t total4 = 0;            // float4s of dW, for the slab sum
+  int flags = 0;                 // the kernel's XSH (ring) / flags (register gather) argument
+  int64_t ws_bytes = 0;          // workspace this kind needs
+};
+
+int dw_table_of(const void* nbr, const void* order) { return !nbr ? DW_NO_TABLE : order ? DW_TABLE : DW_TABLE_NO_ORDER; }
+int dw_align_of(const void* X, const void* dY, const void* dW, const void* ws) {
+  auto is = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+  return (is(X, 16) ? DW_X16 : 0) | (is(X, 8) ? DW_X8 : 0) | (is(dY, 16) ? DW_DY16 : 0) | (is(dW, 16) ? DW_DW16 : 0) |
+         (is(ws, 16) ? DW_WS16 : 0);
+}
+bool dw_bn_supported(int K, int Cin, int Cout) { return dw2_supported(K, Cout, Cin) && Cin % 32 == 0 && Cout % 32 == 0; }
+
+// `wide`: the hint plan (dw2_wide() at a launch).  `sizing`: a size query -- rows and alignment are not known yet, so
+// nothing is empty, nothing is refused for its rows, and the 32-bit limits count as met.
+DwLaunch dw_plan(const DwShape& s, bool wide, bool sizing = false) {
+  DwLaunch p;
+  auto refuse = [&](const char* why) { return p.why = why, p; };
+  auto empty = [&]() { return p.kind = DW_EMPTY, p; };
+  const bool all16 = (s.align & DW_ALL16) == DW_ALL16;
+  // the wave-autonomous kernels slice `rows`, gather 32-channel chunks of `cg` channels and own 32-channel blocks of `co`
+  const int64_t rows = s.swapped ? s.M_in : s.M_out;
+  const int cg = s.swapped ? s.Cout : s.Cin, co = s.swapped ? s.Cin : s.Cout;
+  auto dw2_family = [&](DwKind kind) {
+    p.NOG = (s.K + GS - 1) / GS;
+    p.P = dw2_P_plan(rows, s.K, cg, co, wide);
+    p.gx = (unsigned)p.P;
+    p.gy = (unsigned)(p.NOG * (cg / 32) * ((co + 31) / 32));
+    p.total4 = (int64_t)s.K * s.Cin * s.Cout / 4;
+    p.ws_bytes = (int64_t)p.P * s.K * s.Cin * s.Cout * (int64_t)sizeof(float) + 256;
+    if (kind == DW_RING) {
+      // (read per call: in-process A/Bs flip them) XCD-aware dealing of the slices: rows >= WSIS_DW2_XCD (0 = never)
+      const int64_t xcd_rows = dw2_env("WSIS_DW2_XCD", 0);     // measured at one scene: no gain at level 0, slower below (chunk imbalance)
+      if (xcd_rows > 0 && s.M_out >= xcd_rows && p.P % 8 == 0) kind = DW_RING_XCD;
+    }
+    p.kind = kind;
+    p.lds = (int64_t)(kind == DW_DW3 ? WAVE_LDS3 : WAVE_LDS) * WGW;
+    // (bit 8 of the ring kernel's XSH argument: the header's table block by one 16-byte DMA instead of four 4-byte ones)
+    p.flags = kind == DW_DW3       ? dw3_flags(s.M_out)
+              : kind == DW_SWAPPED ? XSH_DEFAULT
+                                   : dw2_env("WSIS_DW2_XSH", XSH_DEFAULT) | (dw3_h16(s.M_out) ? 256 : 0);
+    return p;
+  };
+  if (s.swapped) {
+    if (!dw_bn_supported(s.K, s.Cin, s.Cout)) return refuse("needs K <= 32 and channel counts that are multiples of 32");
+    if (!sizing) {
+      if (s.M_in == 0 || s.M_out == 0) return empty();
+      if (s.table != DW_TABLE) return refuse("null pointer");
+      if (!dw2_fits(s.M_out, s.M_in, s.K, s.Cout, s.Cin)) return refuse("tensor too large for 32-bit gather offsets");
+      if (!all16) return refuse("16-byte alignment");
+    }
+    return dw2_family(DW_SWAPPED);
+  }
+  if (!sizing) {
+    if (s.M_out == 0) return empty();
+    if (s.table == DW_NO_TABLE && !(s.K == 1 && s.M_in == s.M_out))
+      return refuse("nbr may be null only for the dense 1x1 case");
+    if (s.M_in * s.Cin * 4 >= ((int64_t)1 << 32) || s.M_out * s.Cout * 4 >= ((int64_t)1 << 32))
+      return refuse("dW addresses features as 32-bit byte offsets: a feature matrix must stay below 4 GiB");
+  }
+  if (dw2_supported(s.K, s.Cin, s.Cout) && (sizing || dw2_fits(s.M_in, s.M_out, s.K, s.Cin, s.Cout)) &&
+      (s.table == DW_TABLE || (s.table == DW_NO_TABLE && s.K == 1 && s.M_in == s.M_out)) && all16)
+    return dw2_family(dw3_mode() && dw3_fits(s.M_in, s.Cin) ? DW_DW3 : DW_RING);
+  if (s.table != DW_NO_TABLE && spconv_in_supported(s.K, s.Cin, s.Cout) && (s.align & DW_X8) && (s.align & DW_DW16) &&
+      (s.align & DW_WS16)) {
+    p.kind = DW_IN_CONV;
+    p.ws_bytes = spconv_in_dw_workspace_bytes(s.M_out);
+    return p;
+  }
+  p.ws_bytes = spconv_dw1_workspace_bytes(s.M_out, s.K, s.Cin, s.Cout);
+  if (p.ws_bytes < 0) return refuse("dW supports kernel volumes up to 128 offsets");
+  p.kind = DW_GENERIC;
+  return p;
+}
+
+// size query: the maximum over the kinds the shape can take with unknown alignment, under both hint plans (the hint may
+// change between sizing and launch); -1 where every launch of the shape is refused
+int64_t dw_size(DwShape s) {
+  int64_t bytes = -1;
+  for (const int align : {(int)DW_ALL16 | DW_X8, 0})
+    for (const bool wide : {false, true}) {
+      s.align = align;
+      const DwLaunch p = dw_plan(s, wide, true);
+      if (p.kind == DW_REFUSED) return -1;
+      bytes = std::max(bytes, p.ws_bytes);
+    }
+  return bytes;
+}
+
+// the dynamic-LDS allowance of one kernel instantiation, asked for once per process (the initialiser of a local static
+// is thread-safe: the weight-gradient worker and the caller's thread both launch)
+template <auto Kernel, int Bytes>
+hipError_t dw_allow_lds() {
+  static const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Bytes);
+  return e;
+}
+constexpr int LDSB = WAVE_LDS * WGW, LDSB3 = WAVE_LDS3 * WGW;
+
+thread_local DwRedRec* t_defer = nullptr;
+
+struct DwArgs {
+  const float* X;
+  const int32_t *nbr, *order;      // own-rows form: the dIn table and its order
+  const float* dY;
+  float* dW;
+  void* ws;
+  DwBn bn;                         // own-rows form only
+};
+
+// launch and finish a planned product: profile record, the plan's kernel, launch check, then the fixed-order slab sum --
+// deferred into the thread's DwRedRec slot where the executor set one -- and the end of the profile record
+int dw_run(const DwLaunch& p, const DwShape& s, const DwArgs& a, hipStream_t st) {
+  if (p.kind == DW_EMPTY) {
+    WSIS_HIP_CHECK(hipMemsetAsync(a.dW, 0, sizeof(float) * (size_t)s.K * s.Cin * s.Cout, st));
+    return WSIS_OK;
+  }
+  float* const partial = static_cast<float*>(a.ws);
+  const dim3 grid(p.gx, p.gy, 1), block(WGW * 64);
+  unsigned long long* const no_dbg = nullptr;
+  int rc = WSIS_OK;
+  ProfScope prof(1, st, p.kind == DW_IN_CONV);
+  switch (p.kind) {
+    case DW_DW3:
+      WSIS_HIP_CHECK((dw_allow_lds<&spconv_dw3_kernel<false>, LDSB3>()));
+      hipLaunchKernelGGL((spconv_dw3_kernel<false>), grid, block, (size_t)p.lds, st, a.X, a.nbr, a.order, a.dY, partial,
+                         s.M_in, s.M_out, s.K, s.Cin, s.Cout, p.NOG, p.flags, no_dbg);
+      break;
+    case DW_RING:
+      WSIS_HIP_CHECK((dw_allow_lds<&spconv_dw2_kernel<false, false>, LDSB>()));
+      hipLaunchKernelGGL((spconv_dw2_kernel<false, false>), grid, block, (size_t)p.lds, st, a.X, a.nbr, a.order, a.dY,
+                         partial, s.M_in, s.M_out, s.K, s.Cin, s.Cout, p.NOG, p.flags, no_dbg);
+      break;
+    case DW_RING_XCD:
+      WSIS_HIP_CHECK((dw_allow_lds<&spconv_dw2_kernel<false, true>, LDSB>()));
+      hipLaunchKernelGGL((spconv_dw2_kernel<false, true>), grid, block, (size_t)p.lds, st, a.X, a.nbr, a.order, a.dY,
+                         partial, s.M_in, s.M_out, s.K, s.Cin, s.Cout, p.NOG, p.flags, no_dbg);
+      break;
+    case DW_SWAPPED:      // kernel roles: gathered = conv dY (rows M_out, channels Cout), own = conv x (rows M_in, channels Cin)
+      WSIS_HIP_CHECK((dw_allow_lds<&spconv_dw2_kernel<false, false, true>, LDSB>()));
+      hipLaunchKernelGGL((spconv_dw2_kernel<false, false, true>), grid, block, (size_t)p.lds, st, a.dY, a.nbr, a.order, a.X,
+                         partial, s.M_out, s.M_in, s.K, s.Cout, s.Cin, p.NOG, p.flags, no_dbg, a.bn);
+      break;
+    case DW_IN_CONV:      // im2col on the matrix cores; the launcher sums its own slabs
+      rc = spconv_in_dw_launch(a.X, a.nbr, a.order, a.dY, a.dW, s.M_out, a.ws, prof.ka(), prof.kb(), st);
+      break;
+    case DW_GENERIC:      // the launcher stops the main part of the record and sums its own slabs
+      rc = spconv_dw1_launch(a.X, a.nbr, a.order, a.dY, a.dW, s.M_in, s.M_out, s.K, s.Cin, s.Cout, a.ws, prof, st);
+      break;
+    default:
+      return fail(WSIS_ERR_ARG, "dw_run: no launch for plan kind %d", (int)p.kind);
+  }
+  prof.stop();
+  if (rc != WSIS_OK) return rc;
+  WSIS_LAUNCH_CHECK();
+  if (p.P) {           // P slabs of a wave-autonomous kernel
+    if (t_defer) {     // the executor finishes this product with the other slab sums of its pass (dw2_reduce_batch)
+      t_defer->partial = partial;
+      t_defer->dW = a.dW;
+      t_defer->total4 = p.total4;
+      t_defer->P = p.P;
+      return WSIS_OK;
+    }
+    dw2_launch_reduce(partial, a.dW, p.total4, p.P, st);
+  }
+  prof.tail();
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
 }
 
 }  // namespace
 
 namespace wsis {
 
-bool dw2_supported(int K, int Cin, int Cout) {
-  static int on = -1;
-  if (on < 0) on = dw2_env("WSIS_DW2", 1);
-  return on && K >= 1 && K <= 32 && Cin >= 32 && Cin % 32 == 0 && Cout >= 4 && Cout % 4 == 0;     // (16-byte dY pieces)
-}
-
-bool dw2_fits(int64_t M_in, int64_t M_out, int K, int Cin, int Cout) {
-  const int64_t lim = (int64_t)1 << 31;
-  return M_in * Cin * 4 < lim && M_out * Cout * 4 < lim && (int64_t)K * M_out * 4 < lim && M_in >= 1 && M_out >= 1;
-}
-
-int64_t dw2_workspace_bytes(int64_t M_out, int K, int Cin, int Cout) {      // (either plan: the hint may change between sizing and launch)
-  const int P = std::max(dw2_P_plan(M_out, K, Cin, Cout, false), dw2_P_plan(M_out, K, Cin, Cout, true));
-  return (int64_t)P * K * Cin * Cout * (int64_t)sizeof(float) + 256;
-}
-
 void dw2_set_batch_rows(int64_t rows) { g_batch_rows.store(rows, std::memory_order_relaxed); }
 int64_t dw2_batch_rows() { return g_batch_rows.load(std::memory_order_relaxed); }
 
-static thread_local DwRedRec* t_defer = nullptr;
 void dw2_set_defer(DwRedRec* slot) { t_defer = slot; }
 
 int dw2_reduce_batch(const DwRedRec* recs, int n, hipStream_t st) {
@@ -1069,178 +1284,105 @@ int dw2_reduce_batch(const DwRedRec* recs, int n, hipStream_t st) {
   return WSIS_OK;
 }
 
-// the own-rows form (kernel SWAP): conv input x [M_in, Cin] normalised on the fly, gathered conv dY [M_out, Cout] through
-// the dIn table (rows = conv inputs); writes dW [K, Cin, Cout] exactly like dw2_launch
-int dw2_launch_swapped(const float* d_X, const float* d_mean, const float* d_var, const float* d_gamma, const float* d_beta,
-                       float eps, int relu, const int32_t* d_nbr_b, const int32_t* d_order_b, int flip, const float* d_dY,
-                       float* d_dW, int64_t M_in, int64_t M_out, int K, int Cin, int Cout, void* d_ws, hipStream_t st) {
-  // kernel roles: gathered = conv dY (rows M_out, channels Cout), own = conv x (rows M_in, channels Cin)
-  const int NOG = (K + GS - 1) / GS;
-  const int P = dw2_P(M_in, K, Cout, Cin);
-  float* partial = static_cast<float*>(d_ws);
-  const dim3 grid((unsigned)P, (unsigned)(NOG * (Cout / 32) * ((Cin + 31) / 32)), 1);
-  const size_t ldsb = (size_t)WAVE_LDS * WGW;
-  static bool attr_set = false;
-  if (!attr_set) {
-    WSIS_HIP_CHECK(hipFuncSetAttribute((const void*)spconv_dw2_kernel<false, false, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-    attr_set = true;
-  }
-  DwBn bn;
-  bn.mean = d_mean;
-  bn.var = d_var;
-  bn.gamma = d_gamma;
-  bn.beta = d_beta;
-  bn.eps = eps;
-  bn.relu = relu;
-  bn.flip = flip;
-  ProfScope prof(1, st);
-  hipLaunchKernelGGL((spconv_dw2_kernel<false, false, true>), grid, dim3(WGW * 64), ldsb, st, d_dY, d_nbr_b, d_order_b, d_X,
-                     partial, M_out, M_in, K, Cout, Cin, NOG, XSH_DEFAULT, (unsigned long long*)nullptr, bn);
-  prof.stop();
-  WSIS_LAUNCH_CHECK();
-  const int64_t total4 = (int64_t)K * Cin * Cout / 4;
-  if (t_defer) {      // the executor finishes this product with the other slab sums of its pass (dw2_reduce_batch)
-    t_defer->partial = partial;
-    t_defer->dW = d_dW;
-    t_defer->total4 = total4;
-    t_defer->P = P;
-    return WSIS_OK;
-  }
-  dw2_launch_reduce(partial, d_dW, total4, P, st);
-  prof.tail();
-  WSIS_LAUNCH_CHECK();
-  return WSIS_OK;
-}
-
-// the register-gather kernel applies when row ids fit 24 bits (v_mad_u32_u24) and a missing pair's offset
-// (0xFFFFFF x pitch mod 2^32) lies beyond the gathered tensor, so that it reads zeros
-bool dw3_fits(int64_t M_in, int Cin) {
-  const uint64_t p = (uint64_t)Cin * 4u;
-  const uint32_t w = (uint32_t)(0xFFFFFFull * p);
-  return M_in < (1 << 24) - 1 && (uint64_t)w >= (uint64_t)M_in * p && w <= 0xFFFFFF00u;
-}
-// WSIS_DW3 (read per call): 1 (default) = spconv_dw3_kernel where it fits, 0 = spconv_dw2_kernel everywhere.  Alone on the
-// GPU the two kernels are at parity (profiles/r06_dw3.txt); IN THE STEP the register-gather kernel wins because of what it
-// does not occupy: 26 KB of LDS per workgroup instead of 77 KB -- the dIn items that share its CU from the main stream
-// (37 KB each at levels 1-2, 8.4 KB at level 0) keep their occupancy: 7.77 -> 7.66 ms at one scene, 11.75 -> 11.67 at two,
-// 20.37 -> 20.06 at four (profiles/r06_ab_dw3_lds.txt; with a 66 KB epilogue the same kernel measured 20.40 vs 20.35)
-int dw3_mode() {
-  const char* e = getenv("WSIS_DW3");
-  return e ? atoi(e) : 1;
-}
-// header table block by ONE 16-byte DMA (both kernels): WSIS_DW_H16 = 1 always (default), 2 only where every table line is
-// 16-byte aligned, 0 never (EXPERIMENTAL build: live)
-bool dw3_h16(int64_t M_out) {
-  const int m = dw2_env("WSIS_DW_H16", 1);
-  return m == 1 || (m == 2 && (M_out & 3) == 0);
-}
-int dw3_flags(int64_t M_out) { return (dw3_h16(M_out) ? 1 : 0) | (dw2_env("WSIS_DW_BAL", 1) ? 2 : 0); }
-
-int dw2_launch(const float* d_X, const int32_t* d_nbr, const int32_t* d_order, const float* d_dY, float* d_dW,
-               int64_t M_in, int64_t M_out, int K, int Cin, int Cout, void* d_ws, hipStream_t st) {
-  const int NOG = (K + GS - 1) / GS;
-  const int P = dw2_P(M_out, K, Cin, Cout);
-  float* partial = static_cast<float*>(d_ws);
-  const dim3 grid((unsigned)P, (unsigned)(NOG * (Cin / 32) * ((Cout + 31) / 32)), 1);
-  if (dw3_mode() && dw3_fits(M_in, Cin)) {
-    const size_t ldsb3 = (size_t)WAVE_LDS3 * WGW;
-    static bool attr3_set = false;
-    if (!attr3_set) {
-      WSIS_HIP_CHECK(hipFuncSetAttribute((const void*)spconv_dw3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)ldsb3));
-      attr3_set = true;
-    }
-    ProfScope prof(1, st);
-    hipLaunchKernelGGL((spconv_dw3_kernel<false>), grid, dim3(WGW * 64), ldsb3, st, d_X, d_nbr, d_order, d_dY, partial, M_in,
-                       M_out, K, Cin, Cout, NOG, dw3_flags(M_out), (unsigned long long*)nullptr);
-    prof.stop();
-    WSIS_LAUNCH_CHECK();
-    const int64_t total4 = (int64_t)K * Cin * Cout / 4;
-    if (t_defer) {
-      t_defer->partial = partial;
-      t_defer->dW = d_dW;
-      t_defer->total4 = total4;
-      t_defer->P = P;
-      return WSIS_OK;
-    }
-    dw2_launch_reduce(partial, d_dW, total4, P, st);
-    prof.tail();
-    WSIS_LAUNCH_CHECK();
-    return WSIS_OK;
-  }
-  const size_t ldsb = (size_t)WAVE_LDS * WGW;
-  static bool attr_set = false;
-  if (!attr_set) {
-    WSIS_HIP_CHECK(hipFuncSetAttribute((const void*)spconv_dw2_kernel<false, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-    WSIS_HIP_CHECK(hipFuncSetAttribute((const void*)spconv_dw2_kernel<false, false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-    attr_set = true;
-  }
-  // (read per call: in-process A/Bs flip them) XCD-aware dealing of the slices: rows >= WSIS_DW2_XCD (0 = never)
-  const int64_t xcd_rows = dw2_env("WSIS_DW2_XCD", 0);     // measured at one scene: no gain at level 0, slower below (chunk imbalance)
-  const bool xcd_on = xcd_rows > 0 && M_out >= xcd_rows;
-  // (bit 8 of the kernel's XSH argument: the header's table block by one 16-byte DMA instead of four 4-byte ones)
-  const int xsh = dw2_env("WSIS_DW2_XSH", XSH_DEFAULT) | (dw3_h16(M_out) ? 256 : 0);
-  ProfScope prof(1, st);
-  if (xcd_on && P % 8 == 0)
-    hipLaunchKernelGGL((spconv_dw2_kernel<false, true>), grid, dim3(WGW * 64), ldsb, st, d_X, d_nbr, d_order,
-                       d_dY, partial, M_in, M_out, K, Cin, Cout, NOG, xsh, (unsigned long long*)nullptr);
-  else
-    hipLaunchKernelGGL((spconv_dw2_kernel<false, false>), grid, dim3(WGW * 64), ldsb, st, d_X, d_nbr, d_order, d_dY,
-                       partial, M_in, M_out, K, Cin, Cout, NOG, xsh, (unsigned long long*)nullptr);
-  prof.stop();
-  WSIS_LAUNCH_CHECK();
-  const int64_t total4 = (int64_t)K * Cin * Cout / 4;
-  if (t_defer) {      // the executor finishes this product with the other slab sums of its pass (dw2_reduce_batch)
-    t_defer->partial = partial;
-    t_defer->dW = d_dW;
-    t_defer->total4 = total4;
-    t_defer->P = P;
-    return WSIS_OK;
-  }
-  dw2_launch_reduce(partial, d_dW, total4, P, st);
-  prof.tail();
-  WSIS_LAUNCH_CHECK();
-  return WSIS_OK;
-}
-
 }  // namespace wsis
 
-// diagnostic build of the kernel: per-wave cycle stamps (start, loop begin, loop end, end) and step / slice counts,
-// 6 x u64 per wave in launch order; *n_waves receives the wave count.  tools/dw2_stamps.py reads it.
-extern "C" int wsis_debug_dw2_diag(const void* d_X, const void* d_nbr, const void* d_order, const void* d_dY,
-                                   int64_t M_in, int64_t M_out, int K, int Cin, int Cout, void* d_ws, void* d_dbg, int64_t dbg_bytes,
-                                   int64_t* n_waves, void* stream) {
-  WSIS_REQUIRE(wsis::dw2_supported(K, Cin, Cout) && wsis::dw2_fits(M_in, M_out, K, Cin, Cout) &&
-                   ((d_nbr && d_order) || (!d_nbr && K == 1)),
-               "shape not supported by the dw2 kernel");
-  const int NOG = (K + GS - 1) / GS;
-  const int P = dw2_P(M_out, K, Cin, Cout);
-  const dim3 grid((unsigned)P, (unsigned)(NOG * (Cin / 32) * ((Cout + 31) / 32)), 1);
+extern "C" {
+
+int64_t wsis_spconv_dw_workspace_bytes(int64_t M_out, int32_t K, int32_t Cin, int32_t Cout) {
+  if (M_out < 0 || K < 1 || Cin < 1 || Cout < 1) return -1;
+  return dw_size(DwShape{M_out, M_out, K, Cin, Cout, DW_TABLE, 0, false});
+}
+
+int32_t wsis_spconv_dw_bn_supported(int32_t K, int32_t Cin, int32_t Cout) { return dw_bn_supported(K, Cin, Cout) ? 1 : 0; }
+
+int64_t wsis_spconv_dw_bn_workspace_bytes(int64_t M_in, int32_t K, int32_t Cin, int32_t Cout) {
+  if (M_in < 0) return -1;
+  return dw_size(DwShape{M_in, M_in, K, Cin, Cout, DW_TABLE, 0, true});
+}
+
+int wsis_hint_batch_rows(int64_t rows) {
+  WSIS_REQUIRE(rows >= 0, "bad row count");
+  dw2_set_batch_rows(rows);
+  return WSIS_OK;
+}
+
+int wsis_spconv_dw(const float* d_X, const int32_t* d_nbr, const int32_t* d_order, const float* d_dY,
+                   float* d_dW, int64_t M_in, int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, void* d_ws,
+                   int64_t ws_bytes, void* stream) {
+  WSIS_REQUIRE(M_in >= 0 && M_out >= 0 && K >= 1 && Cin >= 1 && Cout >= 1 && d_dW, "bad args");
+  const DwShape s{M_in, M_out, K, Cin, Cout, dw_table_of(d_nbr, d_order), dw_align_of(d_X, d_dY, d_dW, d_ws), false};
+  const DwLaunch p = dw_plan(s, dw2_wide());
+  WSIS_REQUIRE(p.kind != DW_REFUSED, p.why);
+  if (p.kind != DW_EMPTY) {
+    WSIS_REQUIRE(d_X && d_dY && d_ws, "null pointer");
+    WSIS_REQUIRE(ws_bytes >= wsis_spconv_dw_workspace_bytes(M_out, K, Cin, Cout), "workspace too small");
+  }
+  return dw_run(p, s, DwArgs{d_X, d_nbr, d_order, d_dY, d_dW, d_ws, DwBn{}}, as_stream(stream));
+}
+
+// the own-rows form (kernel SWAP): conv input x [M_in, Cin] normalised on the fly, gathered conv dY [M_out, Cout] through
+// the dIn table (rows = conv inputs); writes dW [K, Cin, Cout] exactly like wsis_spconv_dw
+int wsis_spconv_dw_bn(const float* d_X, const float* d_mean, const float* d_var, const float* d_gamma,
+                      const float* d_beta, float eps, int32_t relu, const int32_t* d_nbr_b, const int32_t* d_order_b,
+                      int32_t flip, const float* d_dY, float* d_dW, int64_t M_in, int64_t M_out, int32_t K, int32_t Cin,
+                      int32_t Cout, void* d_ws, int64_t ws_bytes, void* stream) {
+  WSIS_REQUIRE(M_in >= 0 && M_out >= 0 && d_dW, "bad args");
+  const DwShape s{M_in, M_out, K, Cin, Cout, dw_table_of(d_nbr_b, d_order_b), dw_align_of(d_X, d_dY, d_dW, d_ws), true};
+  const DwLaunch p = dw_plan(s, dw2_wide());
+  WSIS_REQUIRE(p.kind != DW_REFUSED, p.why);
+  if (p.kind != DW_EMPTY) {
+    WSIS_REQUIRE(d_X && d_dY && d_ws, "null pointer");
+    WSIS_REQUIRE((d_mean == nullptr) == (d_var == nullptr), "mean and var come in pairs");
+    WSIS_REQUIRE(ws_bytes >= wsis_spconv_dw_bn_workspace_bytes(M_in, K, Cin, Cout), "workspace too small");
+  }
+  const DwBn bn{d_mean, d_var, d_gamma, d_beta, eps, (int)relu, (int)flip};
+  return dw_run(p, s, DwArgs{d_X, d_nbr_b, d_order_b, d_dY, d_dW, d_ws, bn}, as_stream(stream));
+}
+
+// diagnostic (not part of the ABI header; host only, no GPU call): the plan of a weight-gradient launch under the present
+// hint and environment -- dw_plan(), the function the launch itself calls.  has_table: 0 none, 1 table and order, 2 table
+// without order; align_bits: 1 X 16-byte aligned, 2 X 8-byte, 4 dY 16, 8 dW 16, 16 workspace 16; swapped: the form of
+// wsis_spconv_dw_bn.  out8 = {kind (0 empty, 1 register gather, 2 LDS ring, 3 its XCD deal, 4 own rows, 5 input
+// convolution, 6 generic), P, grid.x, grid.y, dynamic LDS bytes, total4, kernel flags, workspace bytes}; -1: the entry
+// point refuses the arguments.  tests/test_dw_plan_host.py, tests/test_gpu_dw_walks.py
+int wsis_debug_dw_plan(int64_t M_in, int64_t M_out, int32_t K, int32_t Cin, int32_t Cout, int32_t has_table,
+                       int32_t align_bits, int32_t swapped, int64_t* out) {
+  if (!out || M_in < 0 || M_out < 0 || K < 1 || Cin < 1 || Cout < 1 || has_table < 0 || has_table > 2) return -1;
+  const DwLaunch p = dw_plan(DwShape{M_in, M_out, K, Cin, Cout, has_table, align_bits, swapped != 0}, dw2_wide());
+  if (p.kind == DW_REFUSED) return -1;
+  const int64_t v[8] = {p.kind, p.P, p.gx, p.gy, p.lds, p.total4, p.flags, p.ws_bytes};
+  std::copy(v, v + 8, out);
+  return 0;
+}
+
+// diagnostic build of the kernel the plan names: per-wave cycle stamps (start, loop begin, loop end, end) and step / slice
+// counts, 10 x u64 per wave in launch order; *n_waves receives the wave count.  tools/dw2_stamps.py reads it.
+int wsis_debug_dw2_diag(const void* d_X, const void* d_nbr, const void* d_order, const void* d_dY, int64_t M_in,
+                        int64_t M_out, int K, int Cin, int Cout, void* d_ws, void* d_dbg, int64_t dbg_bytes,
+                        int64_t* n_waves, void* stream) {
+  const DwShape s{M_in, M_out, K, Cin, Cout, dw_table_of(d_nbr, d_order), dw_align_of(d_X, d_dY, nullptr, d_ws), false};
+  const DwLaunch p = dw_plan(s, dw2_wide());
+  WSIS_REQUIRE(p.kind == DW_DW3 || p.kind == DW_RING || p.kind == DW_RING_XCD, "shape not supported by the dw2 kernel");
+  const dim3 grid(p.gx, p.gy, 1);
   *n_waves = (int64_t)grid.x * grid.y * WGW;
   WSIS_REQUIRE(dbg_bytes >= *n_waves * 80, "stamp buffer too small");
-  if (wsis::dw3_mode() && wsis::dw3_fits(M_in, Cin)) {      // the register-gather kernel's stamps (same record layout)
-    const size_t ldsb3 = (size_t)WAVE_LDS3 * WGW;
-    WSIS_HIP_CHECK(hipFuncSetAttribute((const void*)spconv_dw3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)ldsb3));
-    hipLaunchKernelGGL((spconv_dw3_kernel<true>), grid, dim3(WGW * 64), ldsb3, wsis::as_stream(stream),
-                       static_cast<const float*>(d_X), static_cast<const int32_t*>(d_nbr),
-                       static_cast<const int32_t*>(d_order), static_cast<const float*>(d_dY), static_cast<float*>(d_ws),
-                       M_in, M_out, K, Cin, Cout, NOG, wsis::dw3_flags(M_out), static_cast<unsigned long long*>(d_dbg));
-    WSIS_LAUNCH_CHECK();
-    return WSIS_OK;
+  const float *X = static_cast<const float*>(d_X), *dY = static_cast<const float*>(d_dY);
+  const int32_t *nbr = static_cast<const int32_t*>(d_nbr), *order = static_cast<const int32_t*>(d_order);
+  if (p.kind == DW_DW3) {      // the register-gather kernel's stamps (same record layout)
+    WSIS_HIP_CHECK((dw_allow_lds<&spconv_dw3_kernel<true>, LDSB3>()));
+    hipLaunchKernelGGL((spconv_dw3_kernel<true>), grid, dim3(WGW * 64), (size_t)p.lds, as_stream(stream), X, nbr, order, dY,
+                       static_cast<float*>(d_ws), M_in, M_out, K, Cin, Cout, p.NOG, p.flags,
+                       static_cast<unsigned long long*>(d_dbg));
+  } else {
+    WSIS_REQUIRE(p.P % 8 == 0, "diagnostic build is the XCD-aware variant");
+    WSIS_HIP_CHECK((dw_allow_lds<&spconv_dw2_kernel<true, true>, LDSB>()));
+    hipLaunchKernelGGL((spconv_dw2_kernel<true, true>), grid, dim3(WGW * 64), (size_t)p.lds, as_stream(stream), X, nbr, order,
+                       dY, static_cast<float*>(d_ws), M_in, M_out, K, Cin, Cout, p.NOG, p.flags,
+                       static_cast<unsigned long long*>(d_dbg));
   }
-  WSIS_REQUIRE(P % 8 == 0, "diagnostic build is the XCD-aware variant");
-  const size_t ldsb = (size_t)WAVE_LDS * WGW;
-  WSIS_HIP_CHECK(hipFuncSetAttribute((const void*)spconv_dw2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)ldsb));
-  hipLaunchKernelGGL((spconv_dw2_kernel<true, true>), grid, dim3(WGW * 64), ldsb, wsis::as_stream(stream),
-                     static_cast<const float*>(d_X), static_cast<const int32_t*>(d_nbr),
-                     static_cast<const int32_t*>(d_order), static_cast<const float*>(d_dY), static_cast<float*>(d_ws),
-                     M_in, M_out, K, Cin, Cout, NOG, dw2_env("WSIS_DW2_XSH", XSH_DEFAULT) | (wsis::dw3_h16(M_out) ? 256 : 0),
-                     static_cast<unsigned long long*>(d_dbg));
   WSIS_LAUNCH_CHECK();
   return WSIS_OK;
 }
+
+}  // extern "C"
+

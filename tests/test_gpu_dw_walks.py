@@ -23,6 +23,7 @@ import pytest
 import torch
 
 import conv_ref
+import dw_plan_ref
 import harness
 import wsis_native as _n
 from oracle import spconv_ref as ref
@@ -69,6 +70,10 @@ def _diag(X, nbr, order, dY, K, Cin, Cout):
     _n.check(fn(_n.ptr(X), _n.ptr(nbr), _n.ptr(order), _n.ptr(dY), X.shape[0], M_out, K, Cin, Cout, _n.ptr(ws),
                 _n.ptr(dbg), dbg.numel() * 8, ctypes.byref(nw), _n.stream_ptr()), "dw2_diag")
     torch.cuda.synchronize()
+    # the diagnostic launches the grid of the plan the product itself takes (wsis_debug_dw_plan: dw_plan())
+    p = dw_plan_ref.plan_lib(dw_plan_ref.Case("walk", X.shape[0], M_out, K, Cin, Cout, dw_plan_ref.TABLE,
+                                              dw_plan_ref.ALIGNED, 0, 1, ""))
+    assert nw.value == p["gx"] * p["gy"] * dw_plan_ref.WGW, (nw.value, p)
     return dbg[: nw.value * 10].view(-1, 10).cpu().numpy()
 
 
