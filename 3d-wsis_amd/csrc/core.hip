@@ -60,10 +60,12 @@ __global__ void voxelize_bwd_kernel(const float* __restrict__ dout, const int32_
 }
 
 // ---- a14: row gather -------------------------------------------------------------------------
-template <typename IdxT>
+// VEC: float4 per thread.  The host picks it (C % 4 == 0 and src / out 16-byte aligned, the rule of segment.hip); the
+// scalar form takes every other case -- a contiguous view that starts at an odd element of a flat buffer among them.
+template <typename IdxT, bool VEC>
 __global__ void gather_rows_kernel(const float* __restrict__ src, const IdxT* __restrict__ idx,
                                    float* __restrict__ out, int64_t N, int C) {
-  if ((C & 3) == 0) {
+  if (VEC) {
     const int C4 = C >> 2;
     const int64_t total = N * C4;
     const float4* s4 = reinterpret_cast<const float4*>(src);
@@ -85,6 +87,18 @@ __global__ void gather_rows_kernel(const float* __restrict__ src, const IdxT* __
       out[t] = src[(int64_t)idx[p] * C + c];
     }
   }
+}
+
+template <typename IdxT>
+static void gather_rows_launch(const float* d_src, const IdxT* d_idx, float* d_out, int64_t N, int C, bool vec,
+                               hipStream_t st) {
+  const int block = 256;
+  if (vec)
+    hipLaunchKernelGGL((gather_rows_kernel<IdxT, true>), dim3(grid_for(N * (C >> 2), block)), dim3(block), 0, st, d_src,
+                       d_idx, d_out, N, C);
+  else
+    hipLaunchKernelGGL((gather_rows_kernel<IdxT, false>), dim3(grid_for(N * C, block)), dim3(block), 0, st, d_src, d_idx,
+                       d_out, N, C);
 }
 
 extern "C" {
@@ -126,14 +140,12 @@ int wsis_gather_rows(const float* d_src, const void* d_idx, int32_t idx_is_64, f
   WSIS_REQUIRE(N >= 0 && C > 0, "bad sizes");
   if (N == 0) return WSIS_OK;
   WSIS_REQUIRE(d_src && d_idx && d_out, "null pointer");
-  const int block = 256;
-  const int64_t work = (C & 3) == 0 ? N * (C >> 2) : N * C;
+  const bool vec = (C & 3) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_out)) & 15) == 0;
   if (idx_is_64)
-    hipLaunchKernelGGL(gather_rows_kernel<int64_t>, dim3(grid_for(work, block)), dim3(block), 0,
-                       as_stream(stream), d_src, (const int64_t*)d_idx, d_out, N, C);
+    gather_rows_launch(d_src, (const int64_t*)d_idx, d_out, N, C, vec, as_stream(stream));
   else
-    hipLaunchKernelGGL(gather_rows_kernel<int32_t>, dim3(grid_for(work, block)), dim3(block), 0,
-                       as_stream(stream), d_src, (const int32_t*)d_idx, d_out, N, C);
+    gather_rows_launch(d_src, (const int32_t*)d_idx, d_out, N, C, vec, as_stream(stream));
   WSIS_LAUNCH_CHECK();
   return WSIS_OK;
 }

@@ -14,12 +14,14 @@ import wsis_native as _n
 __all__ = ["scatter", "scatter_sum", "scatter_add", "scatter_mean", "scatter_max", "scatter_min",
            "SegmentCSR", "segment_csr", "segment_csr_batch"]
 
-_RED = {"sum": 0, "add": 0, "mean": 1, "max": 2}
+_RED = {"sum": 0, "add": 0, "mean": 1, "max": 2, "min": 3}      # (3 exists here only: the library's max on -src)
 
 
 class SegmentCSR(object):
     """perm int32 [N] (stable argsort of index) and offsets int32 [S+1]; reusable across calls that share
-    the same index tensor (e.g. superpoint ids for centres and for features)."""
+    the same index tensor (e.g. superpoint ids for centres and for features).  Every id must lie in [0, dim_size):
+    an id outside that range is a caller error that neither build checks (the sort leaves such rows behind
+    offsets[S], the counting form of the batched build puts them in one bucket there)."""
 
     def __init__(self, index, dim_size=None):
         _n.require_cuda(index)
@@ -85,28 +87,44 @@ def segment_csr_batch(pairs):
     return out
 
 
+def _row_width(src):
+    C = 1
+    for d in src.shape[1:]:
+        C *= int(d)
+    return C
+
+
 class _SegmentReduce(Function):
+    """reduce 3 (min) is the library's max of -src with the value negated back as 0 - x, so that an empty segment is +0
+    as under max; its backward is that of max unchanged (the two negations cancel): the gradient goes to the arg row
+    and every other row gets +0."""
+
     @staticmethod
     def forward(ctx, src, csr, reduce):
         x = src.contiguous().float()
+        if reduce == 3:
+            x = -x
+        code = min(reduce, 2)
         N = x.shape[0]
         assert N == csr.N, "src rows != index length"
-        x2 = x.view(N, -1)
-        C = x2.shape[1]
+        C = _row_width(src)
+        x2 = x.view(N, C)             # (not view(N, -1): with N = 0 the width could be any value)
         out = torch.empty((csr.S, C), dtype=torch.float32, device=x.device)
-        argmax = torch.empty((csr.S, C), dtype=torch.int32, device=x.device) if reduce == 2 else None
+        argmax = torch.empty((csr.S, C), dtype=torch.int32, device=x.device) if code == 2 else None
         if C > 0:
             _n.check(_n.hip().wsis_segment_reduce_fwd(_n.ptr(x2), _n.ptr(csr.perm), _n.ptr(csr.offsets),
-                                                      _n.ptr(out), _n.ptr(argmax), N, csr.S, C, reduce,
+                                                      _n.ptr(out), _n.ptr(argmax), N, csr.S, C, code,
                                                       _n.stream_ptr()), "segment_reduce_fwd")
-        ctx.csr, ctx.reduce, ctx.argmax, ctx.in_shape = csr, reduce, argmax, src.shape
+        if reduce == 3:
+            out = 0.0 - out
+        ctx.csr, ctx.reduce, ctx.argmax, ctx.in_shape, ctx.C = csr, reduce, argmax, src.shape, C
         return out.view((csr.S,) + tuple(src.shape[1:]))
 
     @staticmethod
     def backward(ctx, grad):
-        csr, reduce, argmax = ctx.csr, ctx.reduce, ctx.argmax
-        g = grad.contiguous().float().view(csr.S, -1)
-        C = g.shape[1]
+        csr, reduce, argmax = ctx.csr, min(ctx.reduce, 2), ctx.argmax
+        C = ctx.C
+        g = grad.contiguous().float().view(csr.S, C)
         if reduce == 2:
             dsrc = torch.zeros((csr.N, C), dtype=torch.float32, device=g.device)
         else:
@@ -128,8 +146,6 @@ def scatter(src, index, dim=0, out=None, dim_size=None, reduce="sum", csr=None):
     _n.require_cuda(src, index)
     if csr is None:
         csr = SegmentCSR(index, dim_size)
-    if reduce == "min":
-        return -_SegmentReduce.apply(-src, csr, 2)
     if reduce not in _RED:
         raise ValueError(f"unsupported reduce {reduce!r}")
     return _SegmentReduce.apply(src, csr, _RED[reduce])
@@ -146,28 +162,30 @@ def scatter_mean(src, index, dim=0, out=None, dim_size=None):
     return scatter(src, index, dim, out, dim_size, "mean")
 
 
-def _arg_from(src, index, dim_size, sign):
+def _arg_from(src, index, dim_size, reduce):
     csr = SegmentCSR(index, dim_size)
-    x = (sign * src).contiguous().float()
-    val = _SegmentReduce.apply(x, csr, 2)
+    val = _SegmentReduce.apply(src, csr, reduce)
     # recompute arg (int64, torch_scatter returns src.size(dim) for empty segments)
+    x = src.detach().contiguous().float()
+    if reduce == 3:
+        x = -x
     N = x.shape[0]
-    x2 = x.view(N, -1)
+    x2 = x.view(N, _row_width(x))
     out = torch.empty((csr.S, x2.shape[1]), dtype=torch.float32, device=x.device)
     arg = torch.empty((csr.S, x2.shape[1]), dtype=torch.int32, device=x.device)
-    _n.check(_n.hip().wsis_segment_reduce_fwd(_n.ptr(x2.detach()), _n.ptr(csr.perm), _n.ptr(csr.offsets),
+    _n.check(_n.hip().wsis_segment_reduce_fwd(_n.ptr(x2), _n.ptr(csr.perm), _n.ptr(csr.offsets),
                                               _n.ptr(out), _n.ptr(arg), N, csr.S, x2.shape[1], 2,
                                               _n.stream_ptr()), "segment_reduce_fwd")
     arg = arg.long()
     arg[arg < 0] = N
-    return sign * val, arg.view(val.shape)
+    return val, arg.view(val.shape)
 
 
 def scatter_max(src, index, dim=0, out=None, dim_size=None):
     assert dim in (0, -src.dim()) and out is None
-    return _arg_from(src, index, dim_size, 1.0)
+    return _arg_from(src, index, dim_size, 2)
 
 
 def scatter_min(src, index, dim=0, out=None, dim_size=None):
     assert dim in (0, -src.dim()) and out is None
-    return _arg_from(src, index, dim_size, -1.0)
+    return _arg_from(src, index, dim_size, 3)
