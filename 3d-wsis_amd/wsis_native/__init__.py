@@ -192,6 +192,26 @@ _HIP_SIGS = {
     "wsis_pt_geof": (I32, [P, P, I64, I32, P, P, P, P]),
     "wsis_pt_edge_features_workspace_bytes": (I64, [I64, I32]),
     "wsis_pt_edge_features": (I32, [P, P, P, P, I64, I32, I32, F32, P, P, P, P, P, P, P, I64, P]),
+    "wsis_cp_arc_tails": (I32, [P, P, I64, P, P]),
+    "wsis_cp_arcs_workspace_bytes": (I64, [I64]),
+    "wsis_cp_arcs": (I32, [P, P, I64, P, P, P, P, P, I64, P]),
+    "wsis_cp_kmeans_workspace_bytes": (I64, [I64]),
+    "wsis_cp_kmeans": (I32, [P, I32, P, P, P, I64, I64, ctypes.c_uint32, ctypes.c_uint32, I32, I32, P, P, I64, P]),
+    "wsis_cp_capacities": (I32, [P, I32, P, P, I64, I64, P, P, P, P, P]),
+    "wsis_cp_quantize": (I32, [P, I64, P, P, I64, F64, P, P, P, P, P, P]),
+    "wsis_cp_min_cut_workspace_bytes": (I64, [I64, I64]),
+    "wsis_cp_min_cut": (I32, [P, P, P, P, P, P, I64, I64, I32, P, P, P, P, I64, P]),
+    "wsis_cp_activate_workspace_bytes": (I64, [I64]),
+    "wsis_cp_activate": (I32, [P, P, I64, P, P, P, P, I64, I64, P, P, P, P, P, P, P, I64, P]),
+    "wsis_cp_values": (I32, [P, I32, P, P, I64, P, P, P]),
+    "wsis_cp_border_keys": (I32, [P, P, P, I64, I64, P, P]),
+    "wsis_cp_borders": (I32, [P, P, P, P, I64, P, P, I32, F64, I64, I64, P, P, P, P, P]),
+    "wsis_cp_merge_workspace_bytes": (I64, [I64]),
+    "wsis_cp_merge": (I32, [P, P, P, I64, I64, P, P, P, P, I64, P]),
+    "wsis_cp_relabel_workspace_bytes": (I64, [I64]),
+    "wsis_cp_relabel": (I32, [P, I64, P, P, I64, P, I64, P, P, P, P, P, P, I64, P]),
+    "wsis_cp_energy_workspace_bytes": (I64, []),
+    "wsis_cp_energy": (I32, [P, I32, P, P, I64, I64, P, P, P, I64, F64, P, P, P, I64, P]),
     "wsis_mask_overlap_chunk": (I32, []),
     "wsis_mask_overlap_tile_rows": (I32, [I32]),
     "wsis_mask_overlap_workspace_bytes": (I64, [I64, I64, I32]),

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define WSIS_ABI_VERSION 2
+#define WSIS_ABI_VERSION 3
 
 /* error codes */
 #define WSIS_OK 0
@@ -916,8 +916,8 @@ int wsis_gp_edge_features(const float* d_xyz, const int32_t* d_perm, const int32
                           float* d_out, void* stream);
 
 /* ---- the S3DIS partition front end: the array stages of generate_SPG_superpoint (data/S3DIS/partition/
- * partition_S3DIS.py:81-115) before the l0 cut-pursuit solver, which stays the caller's (csrc/partition.hip; driven by
- * wsis_partition).  No floating-point atomics, fixed summation order, uncontracted products: two calls give the same
+ * partition_S3DIS.py:81-115) before the l0 cut-pursuit solver (csrc/partition.hip; driven by wsis_partition; the
+ * solver itself is the wsis_cp_* group below).  No floating-point atomics, fixed summation order, uncontracted products: two calls give the same
  * bytes.  Every index read from a table is clamped to its table before use.
  *
  * wsis_pt_bins: the voxel of every point, libply_c.prune ply_c/ply_c.cpp:311-337.  d_min3 fp32 [3] = the per-axis
@@ -967,6 +967,99 @@ int wsis_pt_edge_features(const float* d_geof, const uint8_t* d_rgb, const int32
                           int32_t k, int32_t k_adj, float lambda, float* d_features, uint32_t* d_source,
                           uint32_t* d_target, float* d_distances, float* d_edge_weight, float* d_mean, void* d_ws,
                           int64_t ws_bytes, void* stream);
+
+/* ---- l0 cut pursuit with L2 fidelity: libcp.cutpursuit of partition_S3DIS.py:110-111 (data/S3DIS/partition/cut-pursuit:
+ * src/cutpursuit.cpp:77-105, include/API.h:959-974, include/CutPursuit.h, include/CutPursuit_L2.h; mode 1, speed 4) as
+ * stages (csrc/cutpursuit.hip; driven by wsis_partition.cut_pursuit).  Node weights are 1.  No
+ * floating-point atomic, fixed summation orders, integer flow: two calls give the same bytes.  No workgroup waits for
+ * another; every loop over launches runs on the host, is bounded and returns WSIS_ERR_OVERFLOW at its bound.  d_source /
+ * d_target int32 [E] < V; d_comp int32 [V] = component of a node; d_comp_off int32 [C+1] / d_comp_nodes int32 [V] = the
+ * nodes of a component, ascending (wsis_segment_csr of d_comp); d_sat uint8 [C] = the saturated flags; d_active uint8
+ * [E] = the edge's two arcs are active (cut).
+ *
+ * wsis_cp_arc_tails / wsis_cp_arcs: the arc pairs of API.h:959-974 (addDoubledge), as a CSR by tail node.  Arc a < E is
+ * source[a] -> target[a], arc a + E its reverse; d_tails int64 [2E] = their tails; d_perm int32 [2E] = the arcs sorted by
+ * tail, stable (the perm of wsis_segment_csr(d_tails)), whose offsets are the CSR's rows.  Per CSR position: d_arc_head,
+ * d_arc_rev (the position of the opposite arc) and d_arc_edge (the input edge).  Repeated edges stay separate arcs. */
+int wsis_cp_arc_tails(const int32_t* d_source, const int32_t* d_target, int64_t E, int64_t* d_tails, void* stream);
+int64_t wsis_cp_arcs_workspace_bytes(int64_t E);
+int wsis_cp_arcs(const int32_t* d_source, const int32_t* d_target, int64_t E, const int32_t* d_perm, int32_t* d_arc_head,
+                 int32_t* d_arc_rev, int32_t* d_arc_edge, void* d_ws, int64_t ws_bytes, void* stream);
+/* CutPursuit_L2.h init_labels: the 2-means of every unsaturated component with more than one node, one workgroup per
+ * component, sums and energies in fp64.  Restart r of main iteration `iteration` draws from a hash of (seed, iteration, r,
+ * smallest node of the component, draw): the first kernel is node (draw 0) % size of the component's ascending order, the
+ * second the first node at which the running sum of squared distances to the first exceeds (draw 1) / 2^32 times their
+ * total (node 0 if none).  kmeans_ite times: label = nearer to kernel 1 than to kernel 0, strictly; kernel 0 = mean of the
+ * labelled nodes, kernel 1 = mean of the others (the reference's order); an empty class ends the iterations.  The restart
+ * with the lowest energy (first among equals) gives d_label uint8 [V]; other nodes get 0. */
+int64_t wsis_cp_kmeans_workspace_bytes(int64_t V);
+int wsis_cp_kmeans(const float* d_features, int32_t D, const int32_t* d_comp_off, const int32_t* d_comp_nodes,
+                   const uint8_t* d_sat, int64_t C, int64_t V, uint32_t seed, uint32_t iteration, int32_t restarts,
+                   int32_t kmeans_ite, uint8_t* d_label, void* d_ws, int64_t ws_bytes, void* stream);
+/* CutPursuit_L2.h compute_center and set_capacities: d_centres fp64 [C,2,D] = the means of the nodes with label 1 and
+ * with label 0; a component with an empty class becomes saturated (d_sat is updated).  d_term fp64 [V] = cost_B -
+ * cost_notB of set_capacities: > 0 is the capacity from the source, < 0 minus the capacity to the sink; 0 in saturated
+ * components (the reference leaves their old capacities). */
+int wsis_cp_capacities(const float* d_features, int32_t D, const int32_t* d_comp_off, const int32_t* d_comp_nodes, int64_t C,
+                       int64_t V, const uint8_t* d_label, uint8_t* d_sat, double* d_centres, double* d_term, void* stream);
+/* The integer capacities of one flow: d_src_cap / d_snk_cap int32 [V] from d_term, d_arc_cap int32 [2E] (CSR positions) =
+ * lam * w of the arc's edge, 0 on active edges (d_active may be NULL), each rint(x / scale).  scale = 2^(e - 30) with the
+ * largest capacity of the call in [2^(e-1), 2^e) (1 if all are 0): a capacity fits int32, the excess of 2^30 nodes int64;
+ * integers come through exactly whenever scale <= 1.  d_scale2 fp64 [2]: [0] = scale, [1] = scratch. */
+int wsis_cp_quantize(const double* d_term, int64_t V, const float* d_edge_weight, const uint8_t* d_active, int64_t E, double lam,
+                     const int32_t* d_arc_edge, int32_t* d_src_cap, int32_t* d_snk_cap, int32_t* d_arc_cap, double* d_scale2,
+                     void* stream);
+/* boost::boykov_kolmogorov_max_flow of CutPursuit_L2.h split: the minimum cut by push-relabel with global relabelling,
+ * first phase (a maximum preflow).  Node v has an arc from the source of d_src_cap[v] and one to the sink of
+ * d_snk_cap[v]; d_arc_off int32 [V+1], d_arc_head / d_arc_rev / d_arc_cap int32 [A] as wsis_cp_arcs gives them (self loops
+ * carry nothing).  d_sink_side uint8 [V] = 1 exactly where the sink is reachable in the residual graph -- the same set for
+ * every maximum preflow; *d_cut int64 = the value of that cut.  Rounds of plain launches: a global relabel to the exact
+ * residual distances, then a bounded number of push/relabel sweeps; *h_rounds (host) = rounds used.  max_rounds reached:
+ * WSIS_ERR_OVERFLOW and no result. */
+int64_t wsis_cp_min_cut_workspace_bytes(int64_t V, int64_t A);
+int wsis_cp_min_cut(const int32_t* d_src_cap, const int32_t* d_snk_cap, const int32_t* d_arc_off, const int32_t* d_arc_head,
+                    const int32_t* d_arc_rev, const int32_t* d_arc_cap, int64_t V, int64_t A, int32_t max_rounds,
+                    uint8_t* d_sink_side, int64_t* d_cut, int32_t* h_rounds, void* d_ws, int64_t ws_bytes, void* stream);
+/* CutPursuit.h activate_edges and compute_connected_components: an unsaturated component whose nodes share one label
+ * becomes saturated (d_sat is updated); an edge whose ends differ in label becomes active; then the connected components
+ * over inactive edges by hooking onto the smaller root and pointer jumping.  d_comp_new int32 [V]: ids 0..count-1 in order
+ * of the components' smallest nodes; d_sat_new uint8 [V] (count entries used): the flag of the component each came from;
+ * *d_count int32; *h_rounds (host) = hooking rounds. */
+int64_t wsis_cp_activate_workspace_bytes(int64_t V);
+int wsis_cp_activate(const int32_t* d_source, const int32_t* d_target, int64_t E, const uint8_t* d_label,
+                     const int32_t* d_comp, const int32_t* d_comp_off, const int32_t* d_comp_nodes, int64_t C, int64_t V,
+                     uint8_t* d_sat, uint8_t* d_active, int32_t* d_comp_new, uint8_t* d_sat_new, int32_t* d_count,
+                     int32_t* h_rounds, void* d_ws, int64_t ws_bytes, void* stream);
+/* CutPursuit.h compute_reduced_graph with CutPursuit_L2.h compute_value and compute_merge_gain.  wsis_cp_values: d_mean
+ * fp64 [C,D] and d_weight fp64 [C] (the node count).  wsis_cp_border_keys: d_keys int64 [E] = min * C + max of the two
+ * components of an edge, INT64_MAX inside a component.  wsis_cp_borders, over the keys sorted stably (d_order int64 = the
+ * edges in that order, d_ukeys int64 [B] the distinct keys, d_border_off int64 [B+1] their rows): d_ba < d_bb int32 [B] the
+ * two components, d_bw fp64 [B] the sum of w over the border's edges in edge order, d_gain fp64 [B] = compute_merge_gain
+ * + lam * d_bw. */
+int wsis_cp_values(const float* d_features, int32_t D, const int32_t* d_comp_off, const int32_t* d_comp_nodes, int64_t C,
+                   double* d_mean, double* d_weight, void* stream);
+int wsis_cp_border_keys(const int32_t* d_source, const int32_t* d_target, const int32_t* d_comp, int64_t E, int64_t C,
+                        int64_t* d_keys, void* stream);
+int wsis_cp_borders(const int64_t* d_ukeys, const int64_t* d_border_off, const int64_t* d_order, const float* d_edge_weight,
+                    int64_t E, const double* d_mean, const double* d_weight, int32_t D, double lam, int64_t B, int64_t C,
+                    int32_t* d_ba, int32_t* d_bb, double* d_bw, double* d_gain, void* stream);
+/* CutPursuit.h merge: the greedy matching of the borders with gain > 0 by (gain descending, index ascending), each
+ * component in one merge at the most, as rounds of borders that beat every live border at both ends.  d_taken uint8 [B];
+ * d_map int32 [C]: the component a component joins (itself if none).  wsis_cp_relabel: the ids after the merges, still in
+ * order of smallest node; a merged component is unsaturated; the edges of a merged border are inactive again. */
+int64_t wsis_cp_merge_workspace_bytes(int64_t C);
+int wsis_cp_merge(const int32_t* d_ba, const int32_t* d_bb, const double* d_gain, int64_t B, int64_t C, uint8_t* d_taken,
+                  int32_t* d_map, int32_t* h_rounds, void* d_ws, int64_t ws_bytes, void* stream);
+int64_t wsis_cp_relabel_workspace_bytes(int64_t C);
+int wsis_cp_relabel(const int32_t* d_map, int64_t C, const int32_t* d_source, const int32_t* d_target, int64_t E,
+                    const int32_t* d_comp, int64_t V, const uint8_t* d_sat, uint8_t* d_active, int32_t* d_comp_new,
+                    uint8_t* d_sat_new, int32_t* d_count, void* d_ws, int64_t ws_bytes, void* stream);
+/* CutPursuit_L2.h compute_energy from the components alone: d_out3 fp64 = {1/2 sum_v |f_v - mean|^2, lam * sum of w over the
+ * edges between components, nodes in saturated components}. */
+int64_t wsis_cp_energy_workspace_bytes(void);
+int wsis_cp_energy(const float* d_features, int32_t D, const int32_t* d_comp, const double* d_mean, int64_t V, int64_t C,
+                   const int32_t* d_source, const int32_t* d_target, const float* d_edge_weight, int64_t E, double lam,
+                   const uint8_t* d_sat, double* d_out3, void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ---- evaluation counts: what evaluation/basic/ins_seg_evaluator.py:70-115 (assign_instances_for_scan),
  * evaluation/basic/instances.py:53-85 (VertInstance.get_instances), utils/eval_s3dis.py:42-112 and
