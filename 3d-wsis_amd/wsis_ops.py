@@ -871,10 +871,16 @@ def _head_parts(head):
     return l1, bn, l2
 
 
+def _raw_ok(t, device):
+    """a tensor whose data_ptr() the library may read as dense fp32 on ``device`` (None: an absent optional tensor)"""
+    return t is None or (t.dtype == torch.float32 and t.device == device and t.is_contiguous())
+
+
 def sp_heads(x, heads, linears=()):
     """outputs of the ``head`` Sequentials and of the bias-free Linear(64,64) layers over x [S,64]; None where the fused
-    operator does not apply (CPU tensors, other widths, SyncBatchNorm, mixed train / eval heads, WSIS_FUSE_HEADS=0): the
-    caller then runs the modules one by one"""
+    operator does not apply: the caller then runs the modules one by one.  It does not apply to CPU tensors, other
+    widths, SyncBatchNorm, mixed train / eval heads, a parameter or running statistic that is not contiguous fp32 on x's
+    device, one row in training mode (BatchNorm1d raises there) and with WSIS_FUSE_HEADS=0."""
     import os
     if (not x.is_cuda or x.dim() != 2 or x.shape[1] != 64 or x.dtype != torch.float32 or x.shape[0] < 1
             or len(heads) + len(linears) > _n.HEADS_MAX or os.environ.get("WSIS_FUSE_HEADS", "1") == "0"):
@@ -889,6 +895,14 @@ def sp_heads(x, heads, linears=()):
     if len(modes) > 1 or len({(bn.eps, bn.momentum) for _, bn, _ in parts}) > 1:
         return None
     training = bool(modes.pop()) if modes else False
+    if training and x.shape[0] == 1:
+        return None
+    for l1, bn, l2 in parts:
+        if not all(_raw_ok(t, x.device) for t in (l1.weight, l1.bias, bn.weight, bn.bias, l2.weight, l2.bias,
+                                                  bn.running_mean, bn.running_var)):
+            return None
+    if not all(_raw_ok(l.weight, x.device) for l in linears):
+        return None
     eps, momentum = (parts[0][1].eps, parts[0][1].momentum) if parts else (1e-5, 0.1)
     tensors, running, couts = [], [], []
     for l1, bn, l2 in parts:
