@@ -6,6 +6,9 @@
 //       test_scannetv2.py:389
 //   bfs_cluster       [UPSTREAM PointGroup bfs_cluster] (no call site in the reference; named by
 //       BASELINE.json north_star)
+//   mesh_merge        [UPSTREAM ScanNet Segmentator segment_mesh, the two sweeps over the sorted edges]
+//       call site in the reference: data/ScanNetV2/prepare_data_inst_ScanNetV2.py:77
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -225,6 +228,61 @@ int wsis_host_graph_bfs(const int32_t* h_label, const uint8_t* h_class_valid, in
     ++ng;
   }
   *n_groups = ng;
+  return WSIS_OK;
+}
+
+// The two sweeps of segmentator.segment_mesh (prepare_data_inst_ScanNetV2.py:77, [UPSTREAM]) over the
+// edges already sorted by (w, edge index): Felzenszwalb-Huttenlocher merging with thr = w + kThresh / size, then every
+// component below segMinVerts joins across its first remaining edge.  All arithmetic fp32.  Union by index of the
+// root met first; the ids do not depend on the rule: they are numbered by each segment's smallest vertex.
+int wsis_host_mesh_merge(const int32_t* h_a, const int32_t* h_b, const float* h_w, int64_t E, int64_t V, float kThresh,
+                         int32_t segMinVerts, int64_t* h_out_ids, int64_t* n_segments) {
+  if (E < 0 || V < 0 || V >= ((int64_t)1 << 31) || !n_segments || (E > 0 && (!h_a || !h_b || !h_w)) ||
+      (V > 0 && !h_out_ids))
+    return fail(WSIS_ERR_ARG, "mesh_merge: bad args");
+  for (int64_t e = 0; e < E; ++e) {
+    if (h_a[e] < 0 || h_a[e] >= V || h_b[e] < 0 || h_b[e] >= V)
+      return fail(WSIS_ERR_ARG, "mesh_merge: edge endpoint out of range");
+    if (e > 0 && h_w[e] < h_w[e - 1]) return fail(WSIS_ERR_ARG, "mesh_merge: edges not sorted by weight");
+  }
+  std::vector<int32_t> parent((size_t)V), size((size_t)V, 1);
+  std::vector<float> thr((size_t)V, kThresh);
+  for (int64_t v = 0; v < V; ++v) parent[v] = (int32_t)v;
+  auto find = [&parent](int32_t v) {
+    int32_t r = v;
+    while (parent[r] != r) r = parent[r];
+    while (parent[v] != r) {
+      const int32_t next = parent[v];
+      parent[v] = r;
+      v = next;
+    }
+    return r;
+  };
+  for (int64_t e = 0; e < E; ++e) {
+    const int32_t ra = find(h_a[e]), rb = find(h_b[e]);
+    const float w = h_w[e];
+    if (ra != rb && w <= thr[ra] && w <= thr[rb]) {
+      parent[rb] = ra;
+      size[ra] += size[rb];
+      thr[ra] = w + kThresh / (float)size[ra];
+    }
+  }
+  for (int64_t e = 0; e < E; ++e) {
+    const int32_t ra = find(h_a[e]), rb = find(h_b[e]);
+    if (ra != rb && (size[ra] < segMinVerts || size[rb] < segMinVerts)) {
+      parent[rb] = ra;
+      size[ra] += size[rb];
+    }
+  }
+  // a root's id is set when its smallest vertex comes by (the sweeps are over: size becomes the id table)
+  std::fill(size.begin(), size.end(), -1);
+  int64_t ns = 0;
+  for (int64_t v = 0; v < V; ++v) {
+    const int32_t r = find((int32_t)v);
+    if (size[r] < 0) size[r] = (int32_t)ns++;
+    h_out_ids[v] = size[r];
+  }
+  *n_segments = ns;
   return WSIS_OK;
 }
 

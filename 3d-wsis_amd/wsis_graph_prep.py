@@ -9,6 +9,8 @@
     face_edges(faces, superpoint)                                  the mesh-face edges of ScanNet :193-202
     edge_features(scene, features, edges, rng)                     the 13 edge features
     build_graph_s3dis(...) / build_graph_scannet(...)              -> wsis_datasets.PlainGraph
+    segment_mesh(vertices, faces)                                  the ScanNet superpoints of a mesh (:77)
+    prepare_scannet_scene(points, faces, ...)                      the array part of :64-91 -> (scene tuple, PlainGraph)
 
 Both builders return what ``PlainGraph.from_igraph`` gives for the reference's graph: vertex attributes ``v``,
 ``semantic_label``, ``instance_label``, ``superpoint_feature``, ``superpoint_offset_vector``, edges in ``sorted(set)``
@@ -355,3 +357,141 @@ def build_graph_scannet(xyz, faces, superpoint, semantic_labels=None, instance_l
         si, ti = labels.sp_instance[eh[:, 0]], labels.sp_instance[eh[:, 1]]
         is1ins = np.where((si == NONE) | (ti == NONE), 0, np.where(si == ti, -1, 1))
         return _graph(S, labels, feats, edges, f, is1ins)
+
+
+# ---- ScanNet mesh superpoints: segmentator.segment_mesh (prepare_data_inst_ScanNetV2.py:77, :157) --------------------
+
+MESH_K_THRESH = 0.01             # kThresh and segMinVerts of the ScanNet Segmentator
+MESH_SEG_MIN_VERTS = 20
+
+
+def _mesh_stage(vertices, faces, device, what, mark=None):
+    """Steps 1-4 of DESIGN.md 4.17 -> (a, b, w, vertex_normals, face_normals, err), device tensors.  ``err`` int32 [2] =
+    (face indices outside [0, V), non-finite coordinates) is not read here: with either count non-zero the rest means
+    nothing (``_mesh_refuse``).  ``mark(stage)``, if given, is called behind the launches of a stage."""
+    dev = vertices.device if torch.is_tensor(vertices) and vertices.is_cuda else _cuda_device(device, what)
+    if not torch.is_tensor(vertices):
+        vertices = np.asarray(vertices)
+    if not torch.is_tensor(faces):
+        faces = np.asarray(faces)
+    if len(vertices.shape) != 2 or vertices.shape[1] != 3 or len(faces.shape) != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: vertices [V,3] and faces [F,3], got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    if V >= 1 << 31 or 3 * F >= 1 << 31:
+        raise ValueError(f"{what}: {V} vertices / {3 * F} face edges do not fit int32")
+    if vertices.dtype not in (torch.float32, np.dtype(np.float32)):
+        raise _n.WsisError(f"{what}: vertices must be float32, got {vertices.dtype}")
+    if faces.dtype not in (torch.int32, torch.int64, np.dtype(np.int32), np.dtype(np.int64)):
+        raise _n.WsisError(f"{what}: faces must be int32 or int64, got {faces.dtype}")
+    if F and not V:
+        raise ValueError(f"{what}: face vertex index outside [0, 0)")
+    with torch.cuda.device(dev):
+        xyz, fc = _to_device(vertices, dev), _to_device(faces, dev, torch.int64)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)                 # noqa: E731
+        fn, vn, a, b, w, err = f32(F, 3), f32(V, 3), i32(3 * F), i32(3 * F), f32(3 * F), i32(2)
+        keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+        lib, st = _n.hip(), _n.stream_ptr()
+        _n.check(lib.wsis_mesh_face_normals(_n.ptr(xyz), V, _n.ptr(fc), F, _n.ptr(fn), _n.ptr(keys), _n.ptr(err), st),
+                 "mesh_face_normals")
+        csr = segment_csr(keys, V)                     # stable: a vertex's row lists its face slots ascending
+        _n.check(lib.wsis_mesh_vertex_normals(_n.ptr(fn), _n.ptr(csr.perm), _n.ptr(csr.offsets), V, F, _n.ptr(vn), st),
+                 "mesh_vertex_normals")
+        if mark is not None:
+            mark("normals")
+        _n.check(lib.wsis_mesh_edge_weights(_n.ptr(xyz), _n.ptr(vn), V, _n.ptr(fc), F, _n.ptr(a), _n.ptr(b), _n.ptr(w), st),
+                 "mesh_edge_weights")
+        if mark is not None:
+            mark("weights")
+    return a, b, w, vn, fn, err
+
+
+def _mesh_refuse(err, what):
+    n_index, n_nonfinite = int(err[0]), int(err[1])
+    if n_index:
+        raise ValueError(f"{what}: {n_index} face vertex indices outside the vertices")
+    if n_nonfinite:
+        raise ValueError(f"{what}: {n_nonfinite} vertices with a non-finite coordinate")
+
+
+def mesh_normals(vertices, faces, device="cuda"):
+    """Steps 1-2 of ``segment_mesh`` on their own -> (face_normals fp32 [F,3], vertex_normals fp32 [V,3]), device tensors"""
+    _, _, _, vn, fn, err = _mesh_stage(vertices, faces, device, "mesh_normals")
+    _mesh_refuse(err.tolist(), "mesh_normals")
+    return fn, vn
+
+
+def mesh_edge_weights(vertices, faces, device="cuda"):
+    """Steps 1-4 of ``segment_mesh`` on their own -> (a int32 [3F], b int32 [3F], w fp32 [3F], vertex_normals fp32 [V,3]),
+    device tensors, the edges in face order (unsorted)"""
+    a, b, w, vn, _, err = _mesh_stage(vertices, faces, device, "mesh_edge_weights")
+    _mesh_refuse(err.tolist(), "mesh_edge_weights")
+    return a, b, w, vn
+
+
+def mesh_merge(a, b, w, n_vertices, kThresh=MESH_K_THRESH, segMinVerts=MESH_SEG_MIN_VERTS):
+    """Steps 6-8 of ``segment_mesh`` on the host (``wsis_host_mesh_merge``; no device is touched): the two sweeps over
+    edges already sorted by (w, edge index) -> (ids int64 [n_vertices], number of segments)"""
+    import ctypes
+    a, b = np.ascontiguousarray(a, dtype=np.int32).reshape(-1), np.ascontiguousarray(b, dtype=np.int32).reshape(-1)
+    w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+    if not len(a) == len(b) == len(w):
+        raise ValueError(f"{len(a)} / {len(b)} edge ends for {len(w)} weights")
+    ids, n_seg = np.empty(int(n_vertices), np.int64), ctypes.c_int64(0)
+    _n.check_host(_n.host().wsis_host_mesh_merge(a.ctypes.data, b.ctypes.data, w.ctypes.data, len(w), int(n_vertices),
+                                                 float(kThresh), int(segMinVerts), ids.ctypes.data, ctypes.byref(n_seg)),
+                  "mesh_merge")
+    return ids, int(n_seg.value)
+
+
+def segment_mesh(vertices, faces, kThresh=MESH_K_THRESH, segMinVerts=MESH_SEG_MIN_VERTS, device="cuda", _mark=None):
+    """``segmentator.segment_mesh(vertices, faces)`` (ScanNet :77, :157; [UPSTREAM], restated in DESIGN.md 4.17 -- parity
+    with the external binary is not pinned): Felzenszwalb-Huttenlocher segmentation of the mesh edges weighted by the
+    difference of the vertex normals.  ``vertices`` fp32 [V,3], ``faces`` int32 / int64 [F,3] -> int64 [V], dense ids
+    numbered by each segment's smallest vertex.  numpy in: numpy out; tensors in: a device tensor out.
+
+    Normals and weights are kernels (csrc/meshseg.hip), the stable sort is torch's, the two sweeps are a serial
+    recurrence and run on the host: one read-back of the sorted (a, b, w) with the error word, one upload of the ids.
+    Non-finite coordinates, a face index outside [0, V), V >= 2^31 or 3 F >= 2^31 raise ``ValueError``; there is no CPU
+    fallback.  ``_mark(stage)`` is called behind every stage (tools/mesh_segment_bench.py times them with it)."""
+    as_tensor = torch.is_tensor(vertices)
+    mark = _mark if _mark is not None else (lambda stage: None)
+    a, b, w, _, _, err = _mesh_stage(vertices, faces, device, "segment_mesh", _mark)
+    dev, E = w.device, int(w.numel())
+    V = int(vertices.shape[0])
+    with torch.cuda.device(dev):
+        w_sorted, order = torch.sort(w, stable=True)
+        packed = torch.cat([a[order], b[order], w_sorted.view(torch.int32), err])
+        mark("sort")
+        host = packed.cpu().numpy()                                      # the read-back: 12 bytes per edge + the error word
+        mark("read_back")
+        _mesh_refuse(host[3 * E:], "segment_mesh")
+        ids, _ = mesh_merge(host[:E], host[E:2 * E], host[2 * E:3 * E].view(np.float32), V, kThresh, segMinVerts)
+        mark("host_sweeps")
+        if as_tensor:
+            ids = torch.from_numpy(ids).to(dev)
+            mark("upload")
+    return ids
+
+
+def prepare_scannet_scene(points, faces, semantic_labels=None, instance_labels=None, rng=None, device="cuda", scene=""):
+    """The array part of ``f`` / ``f_test`` (ScanNet :64-91, :107-166) from a mesh already read: ``points`` [V,6] = xyz and
+    rgb in 0..255, ``faces`` [F,3].  ``coords`` = xyz - mean, ``colors`` = rgb / 127.5 - 1, ``superpoint`` =
+    ``segment_mesh(float32(xyz), faces)``, and the graph of ``build_graph_scannet`` on the uncentred xyz (as float32),
+    the reference passing ``points[:, :3]``.  No labels: zeros for both, as ``f_test`` sets them (:79-80).
+    -> ((coords, colors, semantic_labels, instance_labels, superpoint, scene), PlainGraph), what ``ScenePrep`` /
+    ``DeviceScenePrep.upload`` take.  Reading the PLY is the caller's."""
+    points = np.asarray(points)
+    if points.ndim != 2 or points.shape[1] < 6:
+        raise ValueError(f"points [V,6] = xyz + rgb, got {points.shape}")
+    faces = np.ascontiguousarray(faces)
+    if (semantic_labels is None) != (instance_labels is None):
+        raise ValueError("give both label arrays or neither")
+    if semantic_labels is None:
+        semantic_labels, instance_labels = np.zeros(points.shape[0]), np.zeros(points.shape[0])
+    coords = np.ascontiguousarray(points[:, :3] - points[:, :3].mean(0))
+    colors = np.ascontiguousarray(points[:, 3:6]) / 127.5 - 1
+    xyz = np.ascontiguousarray(points[:, :3], dtype=np.float32)
+    superpoint = segment_mesh(xyz, faces, device=device)
+    graph = build_graph_scannet(xyz, faces, superpoint, semantic_labels, instance_labels, rng, device=device)
+    return (coords, colors, semantic_labels, instance_labels, superpoint, scene), graph

@@ -2,7 +2,7 @@
 
 Two libraries (built in-tree by ``3d-wsis_amd/csrc/Makefile`` / ``__graft_entry__.build()``):
 
-* ``libwsis_host.so`` -- host-only operators (voxelization_idx, bfs_cluster); safe in forked
+* ``libwsis_host.so`` -- host-only operators (voxelization_idx, bfs_cluster, graph BFS, mesh merge); safe in forked
   DataLoader workers, never initialises HIP.
 * ``libwsis_hip.so``  -- every device operator (hipcc, gfx950).
 
@@ -48,6 +48,7 @@ _HOST_SIGS = {
     "wsis_host_bfs_cluster_count": (I32, [P, P, P, I64, I32, P, P, P, P]),
     "wsis_host_bfs_cluster_fill": (I32, [P, P, I64, I64, I64, P, P]),
     "wsis_host_graph_bfs": (I32, [P, P, I32, P, P, P, P, I64, P, P]),
+    "wsis_host_mesh_merge": (I32, [P, P, P, I64, I64, F32, I32, P, P]),
 }
 
 _HIP_SIGS = {
@@ -212,6 +213,9 @@ _HIP_SIGS = {
     "wsis_cp_relabel": (I32, [P, I64, P, P, I64, P, I64, P, P, P, P, P, P, I64, P]),
     "wsis_cp_energy_workspace_bytes": (I64, []),
     "wsis_cp_energy": (I32, [P, I32, P, P, I64, I64, P, P, P, I64, F64, P, P, P, I64, P]),
+    "wsis_mesh_face_normals": (I32, [P, I64, P, I64, P, P, P, P]),
+    "wsis_mesh_vertex_normals": (I32, [P, P, P, I64, I64, P, P]),
+    "wsis_mesh_edge_weights": (I32, [P, P, I64, P, I64, P, P, P, P]),
     "wsis_mask_overlap_chunk": (I32, []),
     "wsis_mask_overlap_tile_rows": (I32, [I32]),
     "wsis_mask_overlap_workspace_bytes": (I64, [I64, I64, I32]),

@@ -82,6 +82,16 @@ int wsis_host_graph_bfs(const int32_t* h_label, const uint8_t* h_class_valid, in
                         const float* h_centre, const float* h_ins_size, const int32_t* h_adj_off,
                         const int32_t* h_adj, int64_t S, int32_t* h_group, int64_t* n_groups);
 
+/* The serial half of segmentator.segment_mesh [UPSTREAM ScanNet Segmentator], prepare_data_inst_ScanNetV2.py:77 (DESIGN.md
+ * 4.17 steps 6-8; steps 1-5 are wsis_mesh_* below and a stable sort).  h_a / h_b int32 [E], h_w fp32 [E]: the edges
+ * sorted ascending by (w, edge index); an unsorted h_w or an endpoint outside [0, V) is WSIS_ERR_ARG.  Sweep 1: every
+ * vertex a component of size 1 and thr = kThresh; an edge whose roots differ and whose w <= thr of both joins them, and
+ * the new root gets thr = w + kThresh / (float)size (fp32).  Sweep 2, same order: roots that differ join if either has
+ * fewer than segMinVerts vertices.  h_out_ids int64 [V]: dense ids numbered by each segment's smallest vertex;
+ * *n_segments their number.  E = 0 or V = 0 is legal. */
+int wsis_host_mesh_merge(const int32_t* h_a, const int32_t* h_b, const float* h_w, int64_t E, int64_t V, float kThresh,
+                         int32_t segMinVerts, int64_t* h_out_ids, int64_t* n_segments);
+
 /* ------------------------------------------------------------------------------------------ */
 /* libwsis_hip.so : device operators                                                          */
 /* ------------------------------------------------------------------------------------------ */
@@ -1060,6 +1070,32 @@ int64_t wsis_cp_energy_workspace_bytes(void);
 int wsis_cp_energy(const float* d_features, int32_t D, const int32_t* d_comp, const double* d_mean, int64_t V, int64_t C,
                    const int32_t* d_source, const int32_t* d_target, const float* d_edge_weight, int64_t E, double lam,
                    const uint8_t* d_sat, double* d_out3, void* d_ws, int64_t ws_bytes, void* stream);
+
+/* ---- ScanNet mesh superpoints: the data-parallel steps of segmentator.segment_mesh(vertices, faces)
+ * [UPSTREAM ScanNet Segmentator], call sites data/ScanNetV2/prepare_data_inst_ScanNetV2.py:77 and :157 (csrc/meshseg.hip,
+ * wsis_graph_prep.segment_mesh; the definition is restated there, the external binary is not on hand).
+ * All arithmetic fp32, uncontracted, in the written order, division and square root correctly rounded: the outputs equal
+ * tests/mesh_segment_ref.py bit for bit.  No floating-point atomics; two calls give the same bytes.  The sort by weight
+ * (stable) lies between wsis_mesh_edge_weights and wsis_host_mesh_merge and is the caller's.
+ *
+ * wsis_mesh_face_normals (:77, step 1): one thread per face of d_faces int64 [F,3] over d_vertices fp32 [V,3]; d_fnormal
+ * fp32 [F,3] = c / |c| of c = (p2 - p1) x (p3 - p1), 0 where |c| = 0.  d_keys int64 [3F]: d_keys[3 f + slot] = the vertex
+ * of that slot -- wsis_segment_csr(d_keys, 3F, V) is the vertex -> face-slot CSR (stable: a row is in ascending face-slot
+ * order).  d_err int32 [2] (zeroed here) = {face indices outside [0, V), non-finite vertex coordinates (all V vertices are
+ * looked at, used or not)}.  An index outside [0, V) is read as vertex 0: with d_err[0] != 0 the outputs mean nothing.
+ * V = 0 with F > 0 is refused. */
+int wsis_mesh_face_normals(const float* d_vertices, int64_t V, const int64_t* d_faces, int64_t F, float* d_fnormal,
+                           int64_t* d_keys, int32_t* d_err, void* stream);
+/* (:77, step 2) d_vnormal fp32 [V,3]: the running mean n += (n_f - n) * (1 / (cnt + 1)) over the vertex's row of the CSR
+ * d_perm int32 [3F] / d_offsets int32 [V+1], one lane per vertex (the recurrence is sequential); not re-normalised; a
+ * vertex in no face keeps 0. */
+int wsis_mesh_vertex_normals(const float* d_fnormal, const int32_t* d_perm, const int32_t* d_offsets, int64_t V, int64_t F,
+                             float* d_vnormal, void* stream);
+/* (:77, steps 3-4) one thread per edge: face f gives (i1,i2), (i1,i3), (i3,i2) at 3f, 3f+1, 3f+2 (repeated edges stay);
+ * d_a / d_b int32 [3F], d_w fp32 [3F]: with d = (p_b - p_a) / |p_b - p_a| (0 if the length is 0), dot = n_a . n_b and
+ * dot2 = n_b . d:  w = 1 - dot, squared if dot2 > 0. */
+int wsis_mesh_edge_weights(const float* d_vertices, const float* d_vnormal, int64_t V, const int64_t* d_faces, int64_t F,
+                           int32_t* d_a, int32_t* d_b, float* d_w, void* stream);
 
 /* ---- evaluation counts: what evaluation/basic/ins_seg_evaluator.py:70-115 (assign_instances_for_scan),
  * evaluation/basic/instances.py:53-85 (VertInstance.get_instances), utils/eval_s3dis.py:42-112 and
