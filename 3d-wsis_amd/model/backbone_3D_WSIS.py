@@ -41,7 +41,9 @@ class _Head(nn.Sequential):
 
 
 class Network(nn.Module):
-    def __init__(self, param):
+    def __init__(self, param, ecc_config="gru_7_0,f_64,b,r"):
+        """``ecc_config``: the superpoint GNN's config string (graphnet.GraphNetwork); the default is the reference's
+        fixed string, 'lstm_7_0,f_64,b,r' its LSTM variant (graphnet.py:77-92).  The heads expect 64 output features."""
         super().__init__()
         self.input_channel = param.input_channel
         self.use_coords = param.use_coords
@@ -68,7 +70,7 @@ class Network(nn.Module):
                          nn.Linear(cin, cout))
 
         self.linear = head(self.media, self.classes)                       # point semantic
-        self.ecc = graphnet.GraphNetwork("gru_7_0,f_64,b,r", nfeat=self.media, fnet_widths=[13, 32, 128, 64],
+        self.ecc = graphnet.GraphNetwork(ecc_config, nfeat=self.media, fnet_widths=[13, 32, 128, 64],
                                          fnet_orthoinit=True, fnet_llbias=True, fnet_bnidx=2, use_pyg=True,
                                          cuda=True)
         sp_feat_dim = 64

@@ -1,7 +1,8 @@
 """Superpoint graph network 'gru_7_0,f_64,b,r' of 3D-WSIS ("next" row 8f-1): plain-torch
 restatement on top of the HIP segmented mean, same parameter names as the reference so its checkpoints load
-(modules/model/graphnet.py:19-114, modules/model/spg_modules.py:61-121,128-185,207-253; state-dict grammar
-in SURVEY App. B: ``ecc.0._cell.*``, ``ecc.0._fnet.{0,2,4,5,7}``, ``ecc.1``, ``ecc.2``).
+(modules/model/graphnet.py:19-114, modules/model/spg_modules.py:61-121,128-185,207-253,264-318; state-dict grammar
+in SURVEY App. B: ``ecc.0._cell.*``, ``ecc.0._fnet.{0,2,4,5,7}``, ``ecc.1``, ``ecc.2``).  The ``lstm_R_...`` token
+builds the same network around LSTMCellEx.
 """
 import os
 
@@ -142,8 +143,45 @@ class GRUCellEx(nn.GRUCell):
         return newgate + inputgate * (hidden - newgate)
 
 
+class LSTMCellEx(nn.LSTMCell):
+    """LSTM cell with per-row normalisation of the gate pre-activations and an input gate
+    (spg_modules.py:264-318), the cell of the ``lstm_R_...`` configurations.  Unlike GRUCellEx the biases are added
+    BEFORE the row norm (spg_modules.py:298-300).  Gate order i, f, g, o as nn.LSTMCell."""
+
+    def __init__(self, input_size, hidden_size, bias=True, layernorm=True, ingate=True):
+        super().__init__(input_size, hidden_size, bias)
+        self._layernorm = layernorm
+        self._ingate = ingate
+        if ingate:
+            self.add_module("ig", nn.Linear(hidden_size, input_size, bias=True))
+
+    def forward(self, input, hidden):
+        if (input.is_cuda and self._ingate and self._layernorm and self.bias and input.shape[1] == 32
+                and self.hidden_size == 32 and input.shape[0] > 0 and os.environ.get("WSIS_FUSE_GRU", "1") != "0"):
+            import wsis_ops
+            return wsis_ops.lstm_cell_ex(input, hidden[0], hidden[1], self)   # one HIP kernel instead of ~30 launches
+        return self.forward_reference(input, hidden)
+
+    def forward_reference(self, input, hidden):
+        hx, cx = hidden
+        if self._ingate:
+            input = torch.sigmoid(self._modules["ig"](hx)) * input
+        gi = F.linear(input, self.weight_ih, self.bias_ih)
+        gh = F.linear(hx, self.weight_hh, self.bias_hh)
+        if self._layernorm:
+            gi, gh = GRUCellEx._rownorm(gi), GRUCellEx._rownorm(gh)
+        ingate, forgetgate, cellgate, outgate = (gi + gh).chunk(4, 1)
+        ingate, forgetgate, outgate = torch.sigmoid(ingate), torch.sigmoid(forgetgate), torch.sigmoid(outgate)
+        cellgate = torch.tanh(cellgate)
+        cy = forgetgate * cx + ingate * cellgate
+        hy = outgate * torch.tanh(cy)
+        return hy, cy
+
+
 class RNNGraphConvModule(nn.Module):
-    """7 x { edge-conditioned message passing -> GRUCellEx } (spg_modules.py:152-185 with the PyG NNConv of :61-121).
+    """R x { edge-conditioned message passing -> GRUCellEx or LSTMCellEx } (spg_modules.py:152-185 with the PyG NNConv
+    of :61-121).  With an LSTM cell the recurrence carries a cell state: cx starts as zeros of hx's shape, every repeat
+    does hx, cx = cell(inp, (hx, cx)), only the hx are concatenated (:170-183); it runs op by op on both paths.
 
     Direction: a node receives the MEAN over its IN-edges (s -> t) of x[s] @ W_e.  NNConv's constructor names a
     ``flow="target_to_source"`` parameter but never hands it to ``MessagePassing.__init__`` (spg_modules.py:61-72:
@@ -155,6 +193,7 @@ class RNNGraphConvModule(nn.Module):
     def __init__(self, cell, filter_net, nfeat, vv=True, nrepeats=1, cat_all=False):
         super().__init__()
         self._cell = cell
+        self._isLSTM = isinstance(cell, nn.LSTMCell)     # the recurrence carries a cell state (spg_modules.py:137,170-171)
         self._fnet = filter_net
         self._nrepeats = nrepeats
         self._cat_all = cat_all
@@ -164,6 +203,12 @@ class RNNGraphConvModule(nn.Module):
     def set_info(self, gc_info):
         self._gci = gc_info
         self._pre = None
+
+    def _step(self, inp, hx, cx):
+        """one cell evaluation -> (hx, cx); cx is None for the GRU cell"""
+        if self._isLSTM:
+            return self._cell(inp, (hx, cx))
+        return self._cell(inp, hx), None
 
     def _filter_state(self):
         """(h [E,64], W' [32, 65*32]) of the filter-free evaluation: the fnet hidden state of every edge and the last
@@ -225,17 +270,18 @@ class RNNGraphConvModule(nn.Module):
             h, Waug = self._filter_state()
         csr_gat, csr_agg = self._gci.csr(), self._gci.csr_dst()      # gather side = sources, aggregation side = targets
         cell = self._cell
-        if (os.environ.get("WSIS_GNN_LOOP", "1") != "0" and os.environ.get("WSIS_FUSE_GRU", "1") != "0"
+        if (not self._isLSTM and os.environ.get("WSIS_GNN_LOOP", "1") != "0" and os.environ.get("WSIS_FUSE_GRU", "1") != "0"
                 and getattr(cell, "_ingate", False) and getattr(cell, "_layernorm", False) and cell.bias
                 and getattr(cell, "hidden_size", 0) == 32 and hx.shape[0] > 0 and h.shape[0] > 0):
             # the whole recurrence as one autograd node (same kernels, same order)
             return wsis_ops.ecc_gru_loop(hx, h, Waug, cell, csr_agg, csr_gat, self._nrepeats, self._cat_all)
         hxs = [hx]
+        cx = torch.zeros_like(hx) if self._isLSTM else None         # (the LSTM cell runs op by op: no one-node loop yet)
         for _ in range(self._nrepeats):
             U = hx @ Waug                                                  # [S, 65*32]
             msg = wsis_ops.ecc_contract(h, U, csr_gat)                     # [E, 32]: m_e = h_e . U[source_e]
             inp = scatter(msg, tgt, dim=0, dim_size=hx.size(0), reduce="mean", csr=csr_agg)
-            hx = self._cell(inp, hx)
+            hx, cx = self._step(inp, hx, cx)
             hxs.append(hx)
         return torch.cat(hxs, 1) if self._cat_all else hx
 
@@ -257,6 +303,7 @@ class RNNGraphConvModule(nn.Module):
             src_c, dst_c = src.contiguous(), dst.contiguous()
             csr_gat = self._gci.csr()
         hxs = [hx]
+        cx = torch.zeros_like(hx) if self._isLSTM else None
         for _ in range(self._nrepeats):
             if fused:
                 # gather + per-edge mat-vec + mean over the in-edges in ONE kernel (and one for the backward):
@@ -265,15 +312,20 @@ class RNNGraphConvModule(nn.Module):
             else:
                 x_j = hx[src]
                 msg = torch.bmm(x_j.unsqueeze(1), weights).squeeze(1) if weights.dim() == 3 else x_j * weights
-                inp = scatter(msg, dst, dim=0, dim_size=hx.size(0), reduce="mean", csr=csr_agg)
-            hx = self._cell(inp, hx)
+                if hx.is_cuda:
+                    inp = scatter(msg, dst, dim=0, dim_size=hx.size(0), reduce="mean", csr=csr_agg)
+                else:       # (the segmented mean is a device operator; on the host the same mean in plain torch)
+                    deg = torch.bincount(dst, minlength=hx.size(0)).clamp(min=1).to(msg.dtype).unsqueeze(1)
+                    inp = torch.zeros_like(hx).index_add_(0, dst, msg) / deg
+            hx, cx = self._step(inp, hx, cx)
             hxs.append(hx)
         return torch.cat(hxs, 1) if self._cat_all else hx
 
 
 class GraphNetwork(nn.Module):
     """config-string driven container (graphnet.py:39-114); supports the tokens the reference uses:
-    gru_R_vv, f_N, b, r, d_p."""
+    gru_R_vv_layernorm_ingate_catall, lstm_R_vv_layernorm_ingate_catall, f_N, b, r, d_p (not crf: it needs
+    ecc.GraphConvModule)."""
 
     def __init__(self, config, nfeat, fnet_widths, fnet_orthoinit=True, fnet_llbias=True, fnet_bnidx=-1,
                  edge_mem_limit=1e20, use_pyg=True, cuda=True):
@@ -290,7 +342,7 @@ class GraphNetwork(nn.Module):
                 self.add_module(str(d), nn.ReLU(True))
             elif conf[0] == "d":
                 self.add_module(str(d), nn.Dropout(p=float(conf[1]), inplace=False))
-            elif conf[0] == "gru":
+            elif conf[0] == "gru" or conf[0] == "lstm":
                 nrepeats = int(conf[1])
                 vv = bool(int(conf[2])) if len(conf) > 2 else True
                 layernorm = bool(int(conf[3])) if len(conf) > 3 else True
@@ -298,7 +350,8 @@ class GraphNetwork(nn.Module):
                 cat_all = bool(int(conf[5])) if len(conf) > 5 else True
                 fnet = create_fnet(fnet_widths + [nfeat ** 2 if not vv else nfeat], fnet_orthoinit, fnet_llbias,
                                    fnet_bnidx)
-                cell = GRUCellEx(nfeat, nfeat, bias=True, layernorm=layernorm, ingate=ingate)
+                cell_type = GRUCellEx if conf[0] == "gru" else LSTMCellEx
+                cell = cell_type(nfeat, nfeat, bias=True, layernorm=layernorm, ingate=ingate)
                 gconv = RNNGraphConvModule(cell, fnet, nfeat, vv=vv, nrepeats=nrepeats, cat_all=cat_all)
                 self.add_module(str(d), gconv)
                 self.gconvs.append(gconv)

@@ -149,6 +149,9 @@ _HIP_SIGS = {
     "wsis_heads_bwd": (I32, [P, P, I64, I32, P, P, P, I64, P]),
     "wsis_gru_cell_bwd_seq": (I32, [P] * 10 + [I64] + [P] * 8 + [I64, I32, I32, I32, I32, P, I64, P]),
     "wsis_gru_cell_fwd_mean": (I32, [P] * 12 + [I64, I32, P]),
+    "wsis_lstm_cell_workspace_bytes": (I64, [I64]),
+    "wsis_lstm_cell_fwd": (I32, [P] * 11 + [I64, I32, P]),
+    "wsis_lstm_cell_bwd": (I32, [P] * 20 + [I64, I32, P, I64, P]),
     "wsis_affinity_dense_build": (I32, [P, P, P, I64, P, I64, P]),
     "wsis_affinity_transition": (I32, [P, P, P, P, P, I32, F32, P, I64, P]),
     "wsis_dgemm": (I32, [P, P, P, I64, I64, I64, P]),

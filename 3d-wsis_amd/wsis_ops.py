@@ -567,6 +567,52 @@ def gru_cell_ex(x, h, cell):
     return _GruCellEx.apply(x, h, ig.weight, ig.bias, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
 
 
+# ---- fused LSTMCellEx -----------------------------------------------------------------------------------------
+
+class _LstmCellEx(Function):
+    """(hy, cy) = LSTMCellEx(x, (h, c)) with input gate and per-row normalised gates (spg_modules.py:283-310), C == 32.
+    The backward recomputes the forward from the inputs: nothing else is saved."""
+
+    @staticmethod
+    def forward(ctx, x, h, c, w_ig, b_ig, w_ih, w_hh, b_ih, b_hh):
+        _n.require_cuda(x, h, c)
+        args = [t.contiguous().float() for t in (x, h, c, w_ig, b_ig, w_ih, w_hh, b_ih, b_hh)]
+        x = args[0]
+        S, C = x.shape
+        hy, cy = torch.empty_like(x), torch.empty_like(x)
+        _n.check(_n.hip().wsis_lstm_cell_fwd(*[_n.ptr(t) for t in args], _n.ptr(hy), _n.ptr(cy), S, C, _n.stream_ptr()),
+                 "lstm_cell_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*args)
+        return hy, cy
+
+    @staticmethod
+    def backward(ctx, dhy, dcy):
+        args = ctx.saved_tensors
+        x, h, c, w_ig, b_ig, w_ih, w_hh, b_ih, b_hh = args
+        S, C = x.shape
+        lib = _n.hip()
+        # an output without a consumer (the cy of the last repeat) arrives as None: NULL = zero in the kernel
+        dhy = dhy.contiguous().float() if dhy is not None else None
+        dcy = dcy.contiguous().float() if dcy is not None else None
+        dx, dh, dc = torch.empty_like(x), torch.empty_like(h), torch.empty_like(c)
+        dwig, dbig = torch.empty_like(w_ig), torch.empty_like(b_ig)
+        dwih, dwhh = torch.empty_like(w_ih), torch.empty_like(w_hh)
+        dbih, dbhh = torch.empty_like(b_ih), torch.empty_like(b_hh)
+        ws_bytes = lib.wsis_lstm_cell_workspace_bytes(S)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _n.check(lib.wsis_lstm_cell_bwd(*[_n.ptr(t) for t in args], _n.ptr(dhy), _n.ptr(dcy), _n.ptr(dx), _n.ptr(dh),
+                                        _n.ptr(dc), _n.ptr(dwig), _n.ptr(dbig), _n.ptr(dwih), _n.ptr(dwhh), _n.ptr(dbih),
+                                        _n.ptr(dbhh), S, C, _n.ptr(ws), ws_bytes, _n.stream_ptr()), "lstm_cell_bwd")
+        return dx, dh, dc, dwig, dbig, dwih, dwhh, dbih, dbhh
+
+
+def lstm_cell_ex(x, h, c, cell):
+    """fused forward of a graphnet.LSTMCellEx module (layernorm + ingate configuration, 32 channels) -> (hy, cy)"""
+    ig = cell._modules["ig"]
+    return _LstmCellEx.apply(x, h, c, ig.weight, ig.bias, cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
+
+
 # ---- the whole recurrent graph convolution as ONE autograd node -------------------------------------------------
 
 class _EccGruLoop(Function):

@@ -665,6 +665,24 @@ int wsis_gru_cell_fwd_mean(const float* d_m, const int32_t* d_perm, const int32_
                            const float* d_Wig, const float* d_big, const float* d_Wih, const float* d_Whh, const float* d_bih,
                            const float* d_bhh, float* d_hy, int64_t S, int32_t C, void* stream);
 
+/* LSTMCellEx of the superpoint GNN (modules/model/spg_modules.py:264-318: LSTM cell + input gate + per-row
+ * normalisation of the gate pre-activations, the biases inside the norm), C == 32: one kernel forward, one backward +
+ * a fixed-order reduce of the parameter gradients.  Weights in torch.nn.LSTMCell layout: Wih/Whh [4C,C] (i,f,g,o
+ * blocks), Wig [C,C].  Workspace of the backward: spg_modules.py:264-318 has none; here the per-workgroup slabs. */
+int64_t wsis_lstm_cell_workspace_bytes(int64_t S);
+/* (hy, cy) = cell(x, (h, c)), all [S,32] (spg_modules.py:264-318, the branch of :298-310).  S == 0 is a no-op. */
+int wsis_lstm_cell_fwd(const float* d_x, const float* d_h, const float* d_c, const float* d_Wig, const float* d_big,
+                       const float* d_Wih, const float* d_Whh, const float* d_bih, const float* d_bhh, float* d_hy,
+                       float* d_cy, int64_t S, int32_t C, void* stream);
+/* Backward of spg_modules.py:264-318 from the saved inputs (the forward is recomputed).  d_dhy or d_dcy may be NULL
+ * (= zero; not both): the cy of the last repeat has no consumer.  No floating-point atomics: equal inputs give equal
+ * bytes.  S >= 1. */
+int wsis_lstm_cell_bwd(const float* d_x, const float* d_h, const float* d_c, const float* d_Wig, const float* d_big,
+                       const float* d_Wih, const float* d_Whh, const float* d_bih, const float* d_bhh,
+                       const float* d_dhy, const float* d_dcy, float* d_dx, float* d_dh, float* d_dc, float* d_dWig,
+                       float* d_dbig, float* d_dWih, float* d_dWhh, float* d_dbih, float* d_dbhh, int64_t S, int32_t C,
+                       void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---- a17: dense inter-superpoint affinity + label propagation -------------------------------
  * train_scannetv2.py:562-570, modules/datasets/scannetv2_dataset.py:664-721 (fp64, host numpy).
  * A [S,S] fp64 zero-filled then A[u_e, v_e] = aff_e (edge order, later edges win). */
