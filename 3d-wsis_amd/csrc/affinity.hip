@@ -751,7 +751,7 @@ int wsis_dgemm(const double* d_A, const double* d_B, double* d_C, int64_t M, int
                void* stream) {
   WSIS_REQUIRE(M >= 0 && N >= 0 && Kd >= 0, "bad sizes");
   if (M == 0 || N == 0) return WSIS_OK;
-  WSIS_REQUIRE(d_A && d_B && d_C, "null pointer");
+  WSIS_REQUIRE(d_C && (Kd == 0 || (d_A && d_B)), "null pointer");      // (Kd = 0: A and B are empty, C = 0)
   const dim3 grid((unsigned)ceil_div(N, GB), (unsigned)ceil_div(M, GB));
   hipLaunchKernelGGL(dgemm_kernel, grid, dim3(256), 0, as_stream(stream), d_A, d_B, d_C, M, N, Kd);
   WSIS_LAUNCH_CHECK();

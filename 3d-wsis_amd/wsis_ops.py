@@ -219,13 +219,27 @@ def propagate_sparse(A, adj_u8, pred, conf, label, present, class_num, iteration
 
 
 PROP_SPARSE_MAX_S = 8188       # two rows of S doubles + the non-zero list in 160 KB of LDS
+ADJACENCY_MAX = 255            # the kernels read adjacency + I as uint8
+
+
+def adjacency_u8(adjacency, S, device):
+    """``adjacency + I`` (scannetv2_dataset.py:681-682) as the contiguous uint8 [S,S] the kernels read.  igraph counts
+    multi-edges, so an entry can exceed 1; one that does not fit a byte (the identity added) would wrap to a small count
+    without a word, so it raises ValueError instead (one read-back per scene, at the stage boundary)."""
+    adj = torch.as_tensor(adjacency, device=device)
+    a32 = adj.to(torch.int32) + torch.eye(S, dtype=torch.int32, device=device)
+    if bool((a32 & ~ADJACENCY_MAX).any()):
+        bad = (a32 & ~ADJACENCY_MAX).nonzero()[0].tolist()
+        raise ValueError(f"adjacency + I must lie in 0..{ADJACENCY_MAX} (stored as uint8): entry {tuple(bad)} is "
+                         f"{int(a32[bad[0], bad[1]])}")
+    return a32.to(torch.uint8).contiguous()
 
 
 def weak_label_propagation(A, adjacency, sp_semantic_value, superpoint_pred_semantic, superpoint_semantic_label,
                            iterations_num, class_num, dense=None):
     """Device version of ScanNetV2Inst_spg.weak_label_propagation up to ``pseudo_label_final``
     (modules/datasets/scannetv2_dataset.py:664-736).  ``adjacency`` is the [S,S] adjacency (without the
-    identity; it is added here like ``:681-682``).  Returns (pseudo_label_final [S] float64 numpy with -100
+    identity; it is added here like ``:681-682``; counts that do not fit uint8 raise ValueError).  Returns (pseudo_label_final [S] float64 numpy with -100
     for unknown, pseudo_label_scores [S]).  Default: the sparse form (``propagate_sparse``); ``dense=True`` (or
     WSIS_PROP_DENSE=1, or S > 8188) runs the per-class dense products on the f64 matrix cores."""
     dev = A.device
@@ -233,8 +247,7 @@ def weak_label_propagation(A, adjacency, sp_semantic_value, superpoint_pred_sema
     if dense is None:
         dense = os.environ.get("WSIS_PROP_DENSE", "0") != "0"
     dense = dense or S > PROP_SPARSE_MAX_S
-    adj = torch.as_tensor(adjacency, device=dev)
-    adj_u8 = (adj.to(torch.int32) + torch.eye(S, dtype=torch.int32, device=dev)).to(torch.uint8).contiguous()
+    adj_u8 = adjacency_u8(adjacency, S, dev)
     pred = torch.as_tensor(superpoint_pred_semantic, device=dev).to(torch.int32).contiguous()
     conf = torch.as_tensor(sp_semantic_value, device=dev).to(torch.float32).contiguous()
     label_np = np.asarray(superpoint_semantic_label)

@@ -694,7 +694,8 @@ int wsis_affinity_dense_build(const int64_t* d_eu, const int64_t* d_ev, const fl
 int wsis_affinity_transition(const double* d_A, const uint8_t* d_adj, const int32_t* d_pred,
                              const float* d_conf, const int32_t* d_label, int32_t cls, float thr,
                              double* d_T0, int64_t S, void* stream);
-/* C = A @ B, fp64 [S,S] row-major on the f64 matrix cores (v_mfma_f64_16x16x4_f64). */
+/* C = A @ B, fp64 [S,S] row-major on the f64 matrix cores (v_mfma_f64_16x16x4_f64).  Kd = 0: A and B hold nothing (they
+ * may be NULL) and C is written as zeros. */
 int wsis_dgemm(const double* d_A, const double* d_B, double* d_C, int64_t M, int64_t N, int64_t Kd,
                void* stream);
 /* column-wise max / first argmax of T restricted to rows with label[r]==c (other rows count as 0):
