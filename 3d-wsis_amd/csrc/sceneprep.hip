@@ -3,6 +3,7 @@
 // wsis_datasets.ScenePrep mirrors in numpy.
 //
 //   data_aug_with_graph, xyz * scale, its bounds             :194-209, :149-152     wsis_sp_affine
+//   elastic :222-249 (PointGroup's distortion), blur / interpolation               wsis_elastic_blur / _apply
 //   crop :252-273 / crop_v2 s3dis_dataset.py:285-319, one round                     wsis_sp_crop_mask
 //   the five boolean-mask gathers and the dtypes of collate_fn :155-160, :176-181   wsis_sp_emit
 //   np.unique(superpoint, return_inverse=True) :169, get_cropped_inst_label :311-330  wsis_sp_tables + wsis_sp_relabel
@@ -28,6 +29,7 @@ constexpr int SP_WAVES = SP_BLOCK / 64;
 constexpr int SP_PER = 4;                        // consecutive points per thread of the mask-ordered passes
 constexpr int SP_TILE = SP_BLOCK * SP_PER;       // points per workgroup there
 constexpr int SP_SCAN_BLOCK = 1024;              // the one workgroup of the id tables
+constexpr int EL_BLOCK = 256;                    // elastic: cells (blur pass) / points (apply) per workgroup
 constexpr int64_t SP_NONE = -100;
 
 // words of the state block (uint64 each)
@@ -116,6 +118,89 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_affine_kernel(const T* __restrict
   }
   const unsigned long long b = __ballot(bad);
   if (lane == 0 && b) atomicAdd(st + ST_BAD, (unsigned long long)__popcll(b));
+}
+
+// ---- elastic :222-249.  The three noise grids are blurred by six passes of the 3-tap box filter (scipy.ndimage.convolve,
+// mode="constant", cval=0: the sum in fp64 in tap order from 0.0, one rounding to fp32 per pass), then every point is
+// displaced by the trilinear interpolation of the grids (scipy's RegularGridInterpolator, fill_value 0).  All of it is
+// fp64 in the written order; with -ffp-contract=off and the correctly rounded fp64 division the result is scipy's bit
+// for bit.
+__global__ __launch_bounds__(EL_BLOCK) void sp_elastic_blur_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                   int64_t cells, int64_t stride, int len) {
+  const int64_t i = (int64_t)blockIdx.x * EL_BLOCK + threadIdx.x;
+  if (i >= cells) return;
+  const double w = (double)(1.0f / 3.0f);
+  const float* g = in + (int64_t)blockIdx.y * cells;             // blockIdx.y: one of the three grids
+  const int64_t k = (i / stride) % len;                          // the cell's coordinate along the pass's axis
+  const double l = k > 0 ? (double)g[i - stride] : 0.0;
+  const double c = (double)g[i];
+  const double r = k < len - 1 ? (double)g[i + stride] : 0.0;
+  out[(int64_t)blockIdx.y * cells + i] = (float)((w * l + w * c) + w * r);
+}
+
+struct I3 {
+  int v[3];
+};
+
+// node k of axis j is first.v[j] + step * k (exact integers); one thread per point
+__global__ __launch_bounds__(EL_BLOCK) void sp_elastic_apply_kernel(double* __restrict__ xyz, int64_t n,
+                                                                    const float* __restrict__ grids, I3 bb, D3 first,
+                                                                    double step, double mag,
+                                                                    unsigned long long* __restrict__ bounds) {
+  const double inf = __longlong_as_double(0x7ff0000000000000ll);
+  double lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+  const int64_t p = (int64_t)blockIdx.x * EL_BLOCK + threadIdx.x;
+  if (p < n) {
+    double x[3], t[3], d[3] = {0.0, 0.0, 0.0};
+    int64_t idx[3];
+    bool inside = true;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      x[j] = xyz[3 * p + j];
+      inside = inside && x[j] >= first.v[j] && x[j] <= first.v[j] + step * (double)(bb.v[j] - 1);
+    }
+    if (inside) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        // c = number of nodes < x (np.searchsorted, side left): an estimate, then exact compares against the nodes
+        int64_t c = (int64_t)((x[j] - first.v[j]) / step) + 1;
+        c = c < 0 ? 0 : (c > bb.v[j] ? bb.v[j] : c);
+        while (c > 0 && first.v[j] + step * (double)(c - 1) >= x[j]) --c;
+        while (c < bb.v[j] && first.v[j] + step * (double)c < x[j]) ++c;
+        int64_t i = c - 1;
+        i = i < 0 ? 0 : (i > bb.v[j] - 2 ? bb.v[j] - 2 : i);
+        const double a = first.v[j] + step * (double)i, b = first.v[j] + step * (double)(i + 1);
+        idx[j] = i;
+        t[j] = (x[j] - a) / (b - a);
+      }
+      const int64_t s1 = bb.v[2], s0 = (int64_t)bb.v[1] * bb.v[2], cells = s0 * bb.v[0];
+      const int64_t base = (idx[0] * bb.v[1] + idx[1]) * bb.v[2] + idx[2];
+#pragma unroll
+      for (int corner = 0; corner < 8; ++corner) {
+        const int cx = (corner >> 2) & 1, cy = (corner >> 1) & 1, cz = corner & 1;
+        const double w = ((cx ? t[0] : 1.0 - t[0]) * (cy ? t[1] : 1.0 - t[1])) * (cz ? t[2] : 1.0 - t[2]);
+        const int64_t o = base + cx * s0 + cy * s1 + cz;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) d[m] += (double)grids[m * cells + o] * w;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double v = x[j] + d[j] * mag;
+      xyz[3 * p + j] = v;
+      lo[j] = v;
+      hi[j] = v;
+    }
+  }
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double l = wave_min(lo[j]), h = wave_max(hi[j]);
+    if (lane == 0 && l <= h) {
+      atomicMin(bounds + j, ordered_bits(l));
+      atomicMax(bounds + 3 + j, ordered_bits(h));
+    }
+  }
 }
 
 // ---- one crop round: x = scaled - min (the reference's `xyz -= xyz.min(0)`), then
@@ -419,6 +504,17 @@ inline D3 d3(const double* h) {
   return r;
 }
 
+// cells of one elastic grid: bb >= 3 per axis and fewer than 2^31 cells per grid; 0 where the shape is refused
+inline int64_t elastic_cells(const int32_t* bb) {
+  int64_t c = 1;
+  for (int j = 0; j < 3; ++j) {
+    if (bb[j] < 3) return 0;
+    c *= bb[j];
+    if (c >= ((int64_t)1 << 31)) return 0;
+  }
+  return c;
+}
+
 }  // namespace
 
 extern "C" {
@@ -453,6 +549,50 @@ int wsis_sp_affine(const void* d_in, int32_t in_f64, const int64_t* d_pick, int6
   else
     hipLaunchKernelGGL(sp_affine_kernel<float>, g, b, 0, as_stream(stream), static_cast<const float*>(d_in), d_pick,
                        n_src, n, a, scale, d_middle, d_scaled, st);
+  WSIS_LAUNCH_CHECK();
+  return WSIS_OK;
+}
+
+int wsis_elastic_blur(float* d_grids, float* d_tmp, const int32_t* h_bb3, void* stream) {
+  WSIS_REQUIRE(d_grids && d_tmp && h_bb3, "null pointer");
+  WSIS_REQUIRE(d_grids != d_tmp, "the workspace is the grids");
+  const int64_t cells = elastic_cells(h_bb3);
+  WSIS_REQUIRE(cells > 0, "a grid side below 3, or 2^31 cells or more");
+  const dim3 g((unsigned)ceil_div(cells, EL_BLOCK), 3), b(EL_BLOCK);
+  float *src = d_grids, *dst = d_tmp;
+  for (int pass = 0; pass < 6; ++pass) {                            // axis 0, 1, 2, 0, 1, 2: the result is in d_grids again
+    const int axis = pass % 3;
+    const int64_t stride = axis == 0 ? (int64_t)h_bb3[1] * h_bb3[2] : (axis == 1 ? (int64_t)h_bb3[2] : 1);
+    hipLaunchKernelGGL(sp_elastic_blur_kernel, g, b, 0, as_stream(stream), src, dst, cells, stride, (int)h_bb3[axis]);
+    WSIS_LAUNCH_CHECK();
+    float* t = src;
+    src = dst;
+    dst = t;
+  }
+  return WSIS_OK;
+}
+
+int wsis_elastic_apply(double* d_xyz, int64_t n, const float* d_grids, const int32_t* h_bb3, int32_t gran, double mag,
+                          void* d_bounds, void* stream) {
+  WSIS_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "bad n");
+  WSIS_REQUIRE(h_bb3 && d_bounds, "null pointer");
+  WSIS_REQUIRE(elastic_cells(h_bb3) > 0, "a grid side below 3, or 2^31 cells or more");
+  WSIS_REQUIRE(gran >= 1, "gran < 1");
+  for (int j = 0; j < 3; ++j)                                      // the nodes are integers fp64 holds exactly
+    WSIS_REQUIRE(((int64_t)h_bb3[j] - 1) * (int64_t)gran < ((int64_t)1 << 52), "grid extent exceeds 2^52");
+  unsigned long long* bounds = static_cast<unsigned long long*>(d_bounds);
+  WSIS_HIP_CHECK(hipMemsetAsync(bounds, 0xff, 3 * sizeof(unsigned long long), as_stream(stream)));   // minima: largest key
+  WSIS_HIP_CHECK(hipMemsetAsync(bounds + 3, 0, 3 * sizeof(unsigned long long), as_stream(stream)));
+  if (n == 0) return WSIS_OK;
+  WSIS_REQUIRE(d_xyz && d_grids, "null pointer");
+  I3 bb;
+  D3 first;
+  for (int j = 0; j < 3; ++j) {
+    bb.v[j] = h_bb3[j];
+    first.v[j] = (double)(-((int64_t)h_bb3[j] - 1) * (int64_t)gran);
+  }
+  hipLaunchKernelGGL(sp_elastic_apply_kernel, dim3((unsigned)ceil_div(n, EL_BLOCK)), dim3(EL_BLOCK), 0,
+                     as_stream(stream), d_xyz, n, d_grids, bb, first, 2.0 * (double)gran, mag, bounds);
   WSIS_LAUNCH_CHECK();
   return WSIS_OK;
 }

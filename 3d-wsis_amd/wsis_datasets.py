@@ -194,9 +194,16 @@ class ScenePrep(object):
     ``config/ScanNet_v2_3D_WSIS.yaml`` (read at ``scannetv2_dataset.py:36-38``)."""
 
     def __init__(self, full_scale=(128, 512), scale=50, max_npoint=250000, aug=True, test_mode=False, seed=None,
-                 crop_version=1, subsample_train=False):
+                 crop_version=1, subsample_train=False, with_elastic=False):
         """``crop_version=2`` / ``subsample_train=True``: the S3DIS variant (``s3dis_dataset.py``: block crop around a
-        random point, :285-319, and a random quarter of the points per training item, :135-144)."""
+        random point, :285-319, and a random quarter of the points per training item, :135-144).  ``with_elastic``
+        (``param_dataset.with_elastic`` :39): the two ``elastic`` calls of PointGroup on the scaled coordinates of an
+        augmented item; off, nothing changes."""
+        self.with_elastic = bool(with_elastic)
+        if self.with_elastic:
+            for gran in (6 * scale // 50, 20 * scale // 50):
+                if isinstance(gran, bool) or not isinstance(gran, (int, np.integer)) or gran < 1:
+                    raise ValueError(f"with_elastic needs an integer scale of at least 9 (grid spacing {gran!r})")
         self.crop_version = int(crop_version)
         self.subsample_train = bool(subsample_train)
         self.full_scale = [int(full_scale[0]), int(full_scale[1])]
@@ -246,6 +253,12 @@ class ScenePrep(object):
         ax = [np.linspace(-(b - 1) * gran, (b - 1) * gran, b) for b in bb]
         interp = [scipy.interpolate.RegularGridInterpolator(ax, n, bounds_error=0, fill_value=0) for n in noise]
         return xyz + np.hstack([i(xyz)[:, None] for i in interp]) * mag
+
+    def elastic_calls(self):
+        """(gran, mag) of the two calls of PointGroup's ``__getitem__`` [UPSTREAM]; none unless switched on and augmenting"""
+        if not (self.with_elastic and self.aug_flag):
+            return ()
+        return ((6 * self.scale // 50, 40 * self.scale / 50), (20 * self.scale // 50, 160 * self.scale / 50))
 
     # -- :252-273 ------------------------------------------------------------------------------------------------
     def crop(self, xyz):
@@ -335,6 +348,8 @@ class ScenePrep(object):
         flag = bool(self.aug_flag)
         xyz_middle = self.data_aug_with_graph(np.asarray(xyz_origin), graph, flag, flag, flag)
         xyz = xyz_middle * self.scale
+        for gran, mag in self.elastic_calls():           # voxel coordinates only: xyz_middle and the graph stay
+            xyz = self.elastic(xyz, gran, mag)
         xyz_offset = xyz.min(0)
         xyz = xyz - xyz_offset
         valid = np.ones(len(xyz_middle), dtype=bool)
@@ -674,7 +689,9 @@ class DeviceScenePrep(ScenePrep):
     in the same order, the per-point work as one pass per stage on a scene that stays in device memory.
 
     Read-backs per item: the six bounds; one count per crop round (``crop_version=2``: with the kept-point minimum, and
-    one row of three doubles for the random centre); one final vector of counts.  ``last_stats`` holds the launches
+    one row of three doubles for the random centre); one final vector of counts; with ``with_elastic`` on an augmented
+    item, the six bounds after each of the two elastic calls (the noise grids are drawn on the host from ``self.rng``,
+    as the host class draws them, and uploaded in one copy per call).  ``last_stats`` holds the launches
     of this file's native entry points (the CSR build's own launches not included) and the read-backs of the last call.
 
     Differences from the host class: instance ids are refused above 65,536; an id outside its table is reported with
@@ -750,6 +767,19 @@ class DeviceScenePrep(ScenePrep):
             bounds = _ordered_to_double(state[:6].cpu().numpy())
             stats["readbacks"] += 1
             mn, mx = bounds[:3].copy(), bounds[3:].copy()
+            for gran, mag in self.elastic_calls():       # elastic :222-249 in place on `scaled`; its bounds replace mn, mx
+                bb = np.maximum(np.abs(mn), np.abs(mx)).astype(np.int32) // gran + 3
+                bb3 = (ctypes.c_int32 * 3)(*[int(b) for b in bb])
+                noise = np.stack([self.rng.randn(bb[0], bb[1], bb[2]).astype("float32") for _ in range(3)])
+                grids = torch.from_numpy(noise).to(dev)
+                tmp, el_bounds = torch.empty_like(grids), torch.empty(6, dtype=torch.int64, device=dev)
+                _n.check(lib.wsis_elastic_blur(_n.ptr(grids), _n.ptr(tmp), bb3, st), "elastic_blur")
+                _n.check(lib.wsis_elastic_apply(_n.ptr(scaled), n, _n.ptr(grids), bb3, int(gran), float(mag),
+                                                _n.ptr(el_bounds), st), "elastic_apply")
+                bounds = _ordered_to_double(el_bounds.cpu().numpy())
+                stats["launches"] += 7
+                stats["readbacks"] += 1
+                mn, mx = bounds[:3].copy(), bounds[3:].copy()
             mask, count, off, rnd = None, n, np.zeros(3), 0
 
             def crop_round(form, a, b):

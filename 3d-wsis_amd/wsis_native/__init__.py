@@ -178,6 +178,8 @@ _HIP_SIGS = {
     "wsis_sp_state_bytes": (I64, []),
     "wsis_sp_state_init": (I32, [P, P]),
     "wsis_sp_affine": (I32, [P, I32, P, I64, I64, P, F64, P, P, P, P]),
+    "wsis_elastic_blur": (I32, [P, P, P, P]),
+    "wsis_elastic_apply": (I32, [P, I64, P, P, I32, F64, P, P]),
     "wsis_sp_crop_mask": (I32, [P, I64, P, I32, P, P, P, P, I32, P]),
     "wsis_sp_emit_workspace_bytes": (I64, [I64, I64, I64]),
     "wsis_sp_emit": (I32, [P, P, I64, I64, I64, P, P, P, P, P, P, P, P, P, I64, I64] + [P] * 9 + [P, I64, P]),

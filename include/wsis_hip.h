@@ -851,6 +851,26 @@ int wsis_sp_state_init(void* d_state, void* stream);
  * may then be NULL too). */
 int wsis_sp_affine(const void* d_in, int32_t in_f64, const int64_t* d_pick, int64_t n_src, int64_t n, const double* h_m9,
                    double scale, double* d_middle, double* d_scaled, void* d_state, void* stream);
+/* elastic :222-249 (s3dis_dataset.py:232-259 is the same method), PointGroup's elastic distortion, on the scaled
+ * coordinates of wsis_sp_affine.  The reference defines the method and reads `with_elastic` (:39) but never calls it; the
+ * call site is PointGroup's [UPSTREAM].  The noise is drawn by the caller (the order of the random draws
+ * is the contract): d_grids fp32 [3, bb0, bb1, bb2], the three grids of `noise` :238 one after the other; h_bb3 HOST
+ * int32 [3], every entry >= 3 and bb0*bb1*bb2 < 2^31.
+ * Blur: the six scipy.ndimage.convolve calls of :239-244 (axis 0, 1, 2, 0, 1, 2; mode="constant", cval=0), one launch per
+ * pass over the three grids: out[i] = fp32((w*in[i-1] + w*in[i]) + w*in[i+1]) along the axis, in fp64 with
+ * w = fp64(fp32(1)/fp32(3)), a neighbour outside the grid counting as 0 -- scipy's result bit for bit.  d_tmp: workspace
+ * of the size of d_grids; the result is in d_grids. */
+int wsis_elastic_blur(float* d_grids, float* d_tmp, const int32_t* h_bb3, void* stream);
+/* Apply: :245-249 in place on d_xyz fp64 [n,3], one thread per point.  Axis j has the nodes -(bb_j-1)*gran + 2*gran*k
+ * (np.linspace :245, exact integers); per axis i = clip(#nodes < x - 1, 0, bb_j-2), t = (x - a[i]) / (a[i+1] - a[i]); the
+ * displacement d_m = sum over the eight corners (cx,cy,cz) = 000, 001, ..., 111 of fp64(grid_m[i0+cx, i1+cy, i2+cz]) *
+ * ((wx*wy)*wz), w = t or 1 - t, from 0.0 (scipy's RegularGridInterpolator :246, bit for bit); a point with a coordinate
+ * outside [a[0], a[last]] on any axis gets d = 0 on all three (fill_value=0); d_xyz[i,m] += d_m * mag.  Indices and weights
+ * are computed once for the three grids.  d_bounds: uint64 [6] in device memory, a block of its own that the call
+ * initialises: the ORDERED keys (see the state block) of the per-column minimum / maximum of the result; n == 0 leaves
+ * them at all-ones / zero.  gran >= 1 and (bb_j-1)*gran < 2^52 (the nodes are integers fp64 holds exactly). */
+int wsis_elastic_apply(double* d_xyz, int64_t n, const float* d_grids, const int32_t* h_bb3, int32_t gran, double mag,
+                          void* d_bounds, void* stream);
 /* One round of crop :252-273 (form 1) or of crop_v2 s3dis_dataset.py:285-319 (form 2) on x = d_scaled - h_min3 (HOST
  * fp64 [3], the decoded minima): form 1, mask_i = all_j(x_ij + a_j >= 0) and all_j(x_ij + a_j < b_j) with a = offset, b =
  * full_scale; form 2, mask_i = a_j <= x_ij <= b_j on columns 0 and 1 (a = lo, b = hi).  One fp64 operation and one
