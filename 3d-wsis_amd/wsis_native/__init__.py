@@ -244,6 +244,9 @@ _HIP_SIGS = {
     "wsis_grad_nonfinite": (I32, [P, P, I64, P, P]),
     "wsis_adamw_step_scaled": (I32, [P, P, I64, F64, F64, F64, F64, F64, P, P, P, P]),
     "wsis_loss_scale_update": (I32, [P, P, P, F64, F64, I32, P]),
+    "wsis_adamw_group_bytes": (I32, []),
+    "wsis_adamw_step_groups": (I32, [P, P, I64, P, I32, P]),
+    "wsis_adamw_step_scaled_groups": (I32, [P, P, I64, P, I32, P, P, P, P]),
     "wsis_run_ops_workspace_bytes": (I64, [P, I32]),
     "wsis_run_ops": (I32, [P, I32, P, I64, P, P]),
     "wsis_run_ops_marked": (I32, [P, I32, P, I64, P, P, I32, P]),

@@ -1214,11 +1214,12 @@ int wsis_disc_loss_bwd(const float* d_x, const int64_t* d_ins_label, const int64
 
 /* ---- optimizer step (train_scannetv2.py:251; AdamW of config/ScanNet_v2_3D_WSIS.yaml:58-61) in one launch.
  * d_segments: device array of {float* p; const float* g; float* m; float* v; int64_t n; float step_size;
- * float inv_sqrt_bc2; float g_clamp; float pad;} (wsis_adamw_segment_bytes() bytes each; n == 0 skips the parameter;
+ * float inv_sqrt_bc2; float g_clamp; int32_t group;} (wsis_adamw_segment_bytes() bytes each; n == 0 skips the parameter;
  * g_clamp > 0 clamps the gradient to [-g_clamp, g_clamp] first and writes it back: train_scannetv2.py:247-249; step_size =
  * lr / (1 - beta1^t), inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t) with t = updates of that parameter so far, this one
  * included); d_blocks int32 [n_blocks,2] = (segment, chunk of wsis_adamw_chunk() elements) for every chunk of every
- * segment.  Update rule of torch.optim.AdamW (decoupled weight decay), fp32. */
+ * segment.  Update rule of torch.optim.AdamW (decoupled weight decay), fp32.  `group` is read by the *_groups entry
+ * points below only. */
 int32_t wsis_adamw_segment_bytes(void);
 int32_t wsis_adamw_chunk(void);
 int wsis_adamw_step(const void* d_segments, const int32_t* d_blocks, int64_t n_blocks, double lr, double beta1,
@@ -1249,6 +1250,24 @@ int wsis_adamw_step_scaled(const void* d_segments, const int32_t* d_blocks, int6
                            const float* d_found_inf, int32_t* d_skipped, void* stream);
 int wsis_loss_scale_update(float* d_scale, int32_t* d_growth_tracker, float* d_found_inf, double growth_factor,
                            double backoff_factor, int32_t growth_interval, void* stream);
+
+/* ---- several parameter groups in the step's one launch.  Replaces torch.optim.AdamW built with more than one
+ * parameter group around train_scannetv2.py:93-94,251 (no weight decay on norm parameters and biases, a lower learning
+ * rate for the pre-trained UNet, a fix_module part added between stages): torch steps group by group, six launches each.
+ * d_groups: device array of n_groups rows {double lr, beta1, beta2, eps, weight_decay} (wsis_adamw_group_bytes() = 40
+ * bytes each), what wsis_adamw_step / wsis_adamw_step_scaled take as arguments; the kernel rounds
+ * (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)eps, (float)(1.0 - beta2) per group as
+ * those entry points do on the host, so one group row gives their bytes.  `group` of a segment (int32, the last 4 of
+ * its 56 bytes) names its row; the caller guarantees 0 <= group < n_groups.  step_groups: step_size and inv_sqrt_bc2 of
+ * a segment are the caller's, from its group's lr and betas.  step_scaled_groups: the corrections come from the group
+ * row's lr, beta1, beta2 and t = t_host - d_skipped[s]; *d_found_inf != 0 skips EVERY group: no parameter, moment or
+ * gradient byte is written and d_skipped[s] += 1 for every segment with n > 0.  wsis_grad_nonfinite serves both. */
+int32_t wsis_adamw_group_bytes(void);
+int wsis_adamw_step_groups(const void* d_segments, const int32_t* d_blocks, int64_t n_blocks, const void* d_groups,
+                           int32_t n_groups, void* stream);
+int wsis_adamw_step_scaled_groups(const void* d_segments, const int32_t* d_blocks, int64_t n_blocks,
+                                  const void* d_groups, int32_t n_groups, const float* d_grad_scale,
+                                  const float* d_found_inf, int32_t* d_skipped, void* stream);
 
 /* ---- op-list executor: one C call issues a recorded forward or backward pass of the sparse UNet ------------
  * Replaces the Python-dispatched module walk of sparse_unet3d.py:103-350 (ResidualBlock.forward / UBlock.forward
