@@ -12,6 +12,12 @@
 // Distances are evaluated with exactly the same fp32 expression as the scan, so the neighbour sets are identical.
 // Points with more than 1000 hits (upstream keeps the 1000 smallest indices) are finished by an ascending
 // wave-wide scan over their batch item.
+//
+// Domain: finite coordinates with |x / (1.001 r)| < 2^31 (the cell index is an int) and fewer than 1024 batch items;
+// inside it the result is the scan's, bit for bit.  The cell key keeps each cell index modulo 2^18 (cell_key masks
+// every field), so cells 2^18 apart along an axis share a key and a bucket.  That is harmless: the 27 cells around a
+// point differ by at most 2 per axis, so their keys stay distinct and no bucket is visited twice; and a point of an
+// aliased cell is at least (2^18 - 2) cells away, which the distance test rejects like any other non-neighbour.
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -32,10 +38,15 @@ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // ---- uniform-grid path ------------------------------------------------------------------------------------
 constexpr int CELL_BITS = 18;                       // per-dimension cell coordinate bits (bias 2^17)
 constexpr int CELL_BIAS = 1 << (CELL_BITS - 1);
+constexpr uint32_t CELL_MASK = (1u << CELL_BITS) - 1u;
+
+// every field is cut to its own bits: an unmasked index outside [-2^17, 2^17) would spill into the neighbouring field
+// and give several of a point's 27 cells one key (their bucket would then be counted more than once)
+__device__ __forceinline__ uint64_t cell_field(int c) { return ((uint32_t)c + (uint32_t)CELL_BIAS) & CELL_MASK; }
 
 __device__ __forceinline__ uint64_t cell_key(int b, int cx, int cy, int cz) {
-  return ((uint64_t)(uint32_t)b << (3 * CELL_BITS)) | ((uint64_t)(uint32_t)(cx + CELL_BIAS) << (2 * CELL_BITS)) |
-         ((uint64_t)(uint32_t)(cy + CELL_BIAS) << CELL_BITS) | (uint64_t)(uint32_t)(cz + CELL_BIAS);
+  return ((uint64_t)(uint32_t)b << (3 * CELL_BITS)) | (cell_field(cx) << (2 * CELL_BITS)) |
+         (cell_field(cy) << CELL_BITS) | cell_field(cz);
 }
 
 __global__ void bq_keys_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ batch_idx, int64_t N,
